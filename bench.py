@@ -13,7 +13,10 @@ N>1 GPUs: the batch axis shards with no data-path collective (weak scaling:
 torch.distributed.run on 127.0.0.1 -- like ParallelRiccatiSolver(problem, num_threads) spawns its own team
 (parallel-solver.hxx:150) -- and fails loudly when fewer than N devices are visible.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps in the schedule `value` is quoted
+in and prints the headline fields; `--full` adds everything else (the other generator, both schedules with per-kernel
+times, the roofline, the parity spot check, the secondary figures and the CPU baseline).  `--dump-outputs DIR` writes
+what the timed steps computed in their last step (dump_outputs).
 """
 from __future__ import annotations
 
@@ -771,6 +774,37 @@ def parity_check(solver, args, mueq, nsample=8):
     return worst, worst_kkt
 
 
+def dump_outputs(solver, path, seed=2024, max_problems=64, max_gain_problems=4, budget=32 << 20):
+    """--dump-outputs: what the last timed step handed a caller of backward + forward, for a fixed sample of the batch
+    (the same problems on every run with the same arguments; the data itself is seeded), one row per sampled problem,
+    float64: the solution (xs, us, vs, lbdas: every stage's vector concatenated, lqrInitializeSolution's order) of up
+    to `max_problems` problems and the gains (feedforward, feedback: every stage's ff, fb row-major, concatenated) of
+    the first `max_gain_problems` of them, each kind held under `budget` bytes (the whole batch is tens of GB)."""
+    solver.sync()
+    sample = np.sort(np.random.default_rng(seed).choice(solver.batch, size=min(max_problems, solver.batch), replace=False))
+    sols = []
+    for b in sample:
+        sols.append([np.concatenate(part) for part in solver.solution(int(b))])
+        if sum(a.nbytes for s in sols for a in s) > budget:
+            sols.pop()
+            break
+    ffs, fbs = [], []
+    for b in sample[:min(max_gain_problems, len(sols))]:
+        ff, fb = solver.gains_all(int(b))
+        ffs.append(np.concatenate(ff))
+        fbs.append(np.concatenate([g.ravel() for g in fb]))
+        if sum(a.nbytes for a in ffs + fbs) > budget:
+            ffs.pop()
+            fbs.pop()
+            break
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: [s[k] for s in sols] for k, name in enumerate(("xs", "us", "vs", "lbdas"))}
+    arrays.update(feedforward=ffs, feedback=fbs)
+    for name, rows in arrays.items():
+        if rows and rows[0].size:
+            np.save(os.path.join(path, f"{name}.npy"), np.stack(rows).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -808,6 +842,15 @@ def main():
                          "schedule the LIBRARY chooses by itself (gar_hip_set_pipeline(-1), what a new solver starts "
                          "with: a caller's default) -- the other schedule is timed beside it (K steps, same data) and "
                          "both figures are in the line")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline: the other generator, both schedules with "
+                         "their per-kernel times, the roofline, the parity spot check against the oracle, the secondary "
+                         "figures (parallel in time, horizon sharded, secondary shapes, batch scan, configs[2], seam, "
+                         "ProxDDP loop) and the CPU baseline, trimmed by --single-generator / --no-cpu / --no-legs / "
+                         "--no-extras / --pmc; without it a run times the steps and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed in their last step as DIR/<name>.npy "
+                         "(float64; a fixed sample of the batch, rank 0's problems)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -872,8 +915,9 @@ def main():
     # large: for seconds after a process has freed tens of GB of HBM the driver's scrubbing of that memory keeps the
     # copy engines busy and every host<->device copy of the seam runs several times slower (measured: 0.92 -> 2.0 ms
     # and 2.3 -> 4.9 ms right after a 57 GB process, back to 0.92 / 2.3 twenty seconds later).
-    seam_line = seam() if (world == 1 and rank == 0 and not args.no_extras) else None
-    ddp_line = proxddp_loop() if (world == 1 and rank == 0 and not args.no_extras) else None
+    extras = args.full and world == 1 and rank == 0 and not args.no_extras
+    seam_line = seam() if extras else None
+    ddp_line = proxddp_loop() if extras else None
     N, nx, nu, mueq = args.horizon, args.nx, args.nu, 1e-14
     dims = [(nx, nu, 0, nx, 0)] * N + [(nx, 0, 0, nx, 0)]
     solver = BatchedRiccatiSolver(dims, nx, batch=args.batch, num_legs=1, device=local_rank)
@@ -882,6 +926,12 @@ def main():
     stream = torch.cuda.Stream()
     torch.cuda.set_stream(stream)
     solver.set_stream(stream.cuda_stream)
+    # `value` is the schedule a caller gets WITHOUT asking: the library's own choice for this batch on this device
+    # (unless --pipeline forces one)
+    solver.set_pipeline(-1)
+    library_default = solver.pipeline
+    solver.set_pipeline(0)
+    sched = library_default if args.pipeline == "auto" else int(args.pipeline)
 
     def step():
         solver.backward_async(mueq)
@@ -929,7 +979,44 @@ def main():
             elapsed = float(t.item())
         return elapsed
 
-    def measure(generator, seed):
+    def headline(elapsed):
+        """the fields of the line every run prints: sweeps/s of the timed steps in schedule `sched`"""
+        sweeps = args.batch * world * args.steps
+        return {
+            "metric": "Riccati sweeps/sec (bwd+fwd), N=256 nx=36 nu=12",
+            "value": sweeps / elapsed,
+            "unit": "sweeps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": f"synthetic (generator {args.generator}, generated on device)",
+            "config": {"workload": f"batched serial-in-time Riccati N={N} nx={nx} nu={nu} nc=0 fp64 "
+                                   f"(BASELINE.json configs[1])",
+                       "batch_per_gpu": args.batch, "kernel": solver.kernel_name,
+                       "schedule": ("pipelined (two half-batches, forward beside backward)" if sched == 2 else "plain") +
+                                   (" = the library's default for this batch (gar_hip_set_pipeline(-1))" if sched == library_default
+                                    else " (forced by --pipeline; the library's default is the other one)"),
+                       "parallelism": f"batch-sharded x{world} (no data-path collective)"}}
+
+    main_seed = 1234 + 7919 * rank
+    if not args.full:
+        synth_device.fill_problems(solver, seed=main_seed, mode=args.generator)
+        torch.cuda.synchronize()
+        elapsed = timed(sched)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(solver, args.dump_outputs)
+        if rank == 0:
+            print(json.dumps(headline(elapsed)))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    def measure(generator, seed, dump=False):
         """the timed steps in the plain schedule and -- where the solver has it -- in the pipelined one, on the same
         data; then the per-kernel durations of each and the slow-path counters of one backward"""
         synth_device.fill_problems(solver, seed=seed, mode=generator)
@@ -943,6 +1030,8 @@ def main():
                     res["pipelined_unavailable"] = str(e)[:160]
                     continue
             elapsed = timed(pipe)
+            if dump and pipe == sched:
+                dump_outputs(solver, args.dump_outputs)
             res[pipe] = {"elapsed": elapsed, "kms": kernel_ms()}
         solver.set_pipeline(0)
         step()
@@ -954,12 +1043,7 @@ def main():
     # parity spot check and everything below run on the data of the headline measurement
     other = "F" if args.generator == "W" else "W"
     second = None if args.single_generator else measure(other, 4321 + 7919 * rank)
-    main_res = measure(args.generator, 1234 + 7919 * rank)
-
-    # `value` is the schedule a caller gets WITHOUT asking: the library's own choice for this batch on this device
-    solver.set_pipeline(-1)
-    library_default = solver.pipeline
-    solver.set_pipeline(0)
+    main_res = measure(args.generator, main_seed, dump=bool(args.dump_outputs) and rank == 0)
 
     def best_of(res):
         """(historical name) the schedule `value` is quoted in: the library's default when it was timed"""
@@ -1022,25 +1106,7 @@ def main():
                                           "per-launch durations are those of HALF-batch launches running together")
             return o
         out = {
-            "metric": "Riccati sweeps/sec (bwd+fwd), N=256 nx=36 nu=12",
-            "value": sweeps / elapsed,
-            "unit": "sweeps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": f"synthetic (generator {args.generator}, generated on device)",
-            "config": {"workload": f"batched serial-in-time Riccati N={N} nx={nx} nu={nu} nc=0 fp64 "
-                                   f"(BASELINE.json configs[1])",
-                       "batch_per_gpu": args.batch, "kernel": solver.kernel_name,
-                       "schedule": ("pipelined (two half-batches, forward beside backward)" if sched == 2 else "plain") +
-                                   (" = the library's default for this batch (gar_hip_set_pipeline(-1))" if sched == library_default
-                                    else " (forced by --pipeline; the library's default is the other one)"),
-                       "parallelism": f"batch-sharded x{world} (no data-path collective)"},
+            **headline(elapsed),
             "schedules": sched_obj(main_res),
             "kernel_ms": {"backward_sweep": bwd_ms, "initial_stage": init_ms, "forward_sweep": fwd_ms,
                           "problems_per_launch": launch_batch},

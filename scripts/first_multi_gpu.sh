@@ -57,7 +57,7 @@ step "4. the batch axis: bench.py --gpus N (weak scaling), horizon_sharded insid
 for n in $RANKS; do
   echo "-- $n ranks --"
   B=$([ $SAME == 1 ] && echo "--batch 64 --steps 2 --warmup 1" || echo "--steps 10 --warmup 2")
-  timeout 1200 python bench.py --gpus $n $EXTRA $B --single-generator --no-cpu --no-extras --pmc off 2> $O/batch_${n}ranks.err | tail -1 > $O/batch_${n}ranks.json
+  timeout 1200 python bench.py --gpus $n $EXTRA $B --single-generator --no-cpu --no-extras --pmc off --full 2> $O/batch_${n}ranks.err | tail -1 > $O/batch_${n}ranks.json
   python - <<PY || { echo "STEP 4 ($n ranks) FAILED: $(tail -3 $O/batch_${n}ranks.err)"; RC=1; }
 import json; d = json.loads(open("$O/batch_${n}ranks.json").read())
 hs = d.get("horizon_sharded")

@@ -7,7 +7,7 @@ echo "== pytest gpu =="; timeout 900 python -m pytest tests -m gpu -q -p no:xdis
 echo "== smoke =="; timeout 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -E "smoke|Error" | tee $O/smoke.log
 echo "== soak =="; SOAK_SEED=r5a SOAK_SECONDS=120 timeout 200 python scripts/soak.py 2>&1 | tail -4 | tee $O/soak_a.log
 SOAK_SEED=r5b SOAK_FOCUS=constrained SOAK_SECONDS=90 timeout 170 python scripts/soak.py 2>&1 | tail -4 | tee $O/soak_b.log
-echo "== bench =="; timeout 400 python bench.py --steps 20 --warmup 2 2> $O/bench.err | tail -1 > $O/bench_default_batch4096.json
+echo "== bench =="; timeout 400 python bench.py --steps 20 --warmup 2 --full 2> $O/bench.err | tail -1 > $O/bench_default_batch4096.json
 python - <<PY
 import json; d=json.loads(open("$O/bench_default_batch4096.json").read())
 print(d["value"], d["config"]["schedule"], d["roofline"]["frac"], {k: (round(v["value"]) if isinstance(v, dict) else v) for k, v in d["schedules"].items()})

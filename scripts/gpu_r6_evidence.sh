@@ -15,7 +15,7 @@ if has tests; then
   echo "== smoke =="; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -E "smoke|Error" | tee $O/smoke.log
 fi
 if has bench; then
-  echo "== bench default =="; timeout 1200 python bench.py --steps 20 --warmup 2 2> $O/bench.err | tail -1 > $O/bench_default_batch4096.json
+  echo "== bench default =="; timeout 1200 python bench.py --steps 20 --warmup 2 --full 2> $O/bench.err | tail -1 > $O/bench_default_batch4096.json
   python - <<PY
 import json; d=json.loads(open("$O/bench_default_batch4096.json").read())
 print(d["value"], d["config"]["schedule"], d["roofline"]["frac"], d["kernel_ms"], {k: (v["value"] if isinstance(v, dict) else v) for k, v in d["schedules"].items()})
@@ -27,7 +27,7 @@ PY
 fi
 if has prof; then
   echo "== rocprof stats of the bench command (no extras) =="
-  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o trace -- python $R/bench.py --steps 20 --warmup 2 --no-cpu --no-legs --no-extras --pmc off --single-generator > $O/prof_bench.log 2>&1)
+  (cd $TMPDIR && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o trace -- python $R/bench.py --steps 20 --warmup 2 --no-cpu --no-legs --no-extras --pmc off --single-generator --full > $O/prof_bench.log 2>&1)
   find $O/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats_batch4096.csv; head -8 $O/kernel_stats_batch4096.csv | cut -c1-170
   tail -1 $O/prof_bench.log | cut -c1-300
 fi

@@ -23,7 +23,7 @@ if has tracepair; then
   timeout 300 python scripts/trace_pair.py 1024 2>&1 | grep -vE "amdgpu.ids" | tee $O/trace_pair.log
 fi
 if has bench; then
-  echo "== bench default =="; timeout 900 python bench.py --steps 20 --warmup 2 2> $O/bench.err | tail -1 > $O/bench_default_batch4096.json
+  echo "== bench default =="; timeout 900 python bench.py --steps 20 --warmup 2 --full 2> $O/bench.err | tail -1 > $O/bench_default_batch4096.json
   python - <<PY
 import json; d=json.loads(open("$O/bench_default_batch4096.json").read())
 print(d["value"], d["config"]["schedule"], d["roofline"]["frac"], d["kernel_ms"], {k: (v["value"] if isinstance(v, dict) else v) for k, v in d["schedules"].items()})

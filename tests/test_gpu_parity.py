@@ -502,8 +502,8 @@ def _bench_line(cmd):
 
 
 def test_bench_contract_single_gpu():
-    """bench.py's JSON line: the driver's contract fields, the roofline and cpu_baseline objects."""
-    d = _bench_line(["bench.py", "--batch", "128", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"])
+    """bench.py --full's JSON line: the driver's contract fields, the roofline and cpu_baseline objects."""
+    d = _bench_line(["bench.py", "--batch", "128", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--full"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                 "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -532,12 +532,51 @@ def test_bench_contract_single_gpu():
     assert isinstance(d["roofline"]["traffic_source"], (dict, str))
 
 
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """bench.py without --full: the headline fields only, the steps asked for; --dump-outputs writes the last timed
+    step's solution and gains of a fixed sample of the batch, the same on a second run, and the same solution the
+    oracle computes for those problems."""
+    args = ["bench.py", "--batch", "128", "--steps", "3", "--warmup", "1"]
+    d = _bench_line(args + ["--dump-outputs", str(tmp_path / "a")])
+    assert set(d) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                      "scaling", "vs_baseline", "dtype", "data", "config"}
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "sweeps/s" and d["dtype"] == "f64"
+    assert abs(d["value"] - 128 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
+    _bench_line(args + ["--dump-outputs", str(tmp_path / "b")])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["feedback.npy", "feedforward.npy", "lbdas.npy", "us.npy", "xs.npy"]
+    out = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert out[n[:-4]].dtype == np.float64 and np.array_equal(out[n[:-4]], np.load(tmp_path / "b" / n)), n
+    N, nx, nu = 256, 36, 12
+    assert out["xs"].shape == (64, (N + 1) * nx) and out["us"].shape == (64, N * nu)
+    assert out["feedback"].shape[0] == 4 and np.isfinite(out["feedback"]).all()
+    # the sample's first problem, regenerated (same seed, same generator) and solved by the oracle
+    from aligator_amd import synth_device
+    from aligator_amd.gar import BatchedRiccatiSolver
+    from oracle import oracle as ora
+    b = int(np.sort(np.random.default_rng(2024).choice(128, size=64, replace=False))[0])
+    s = BatchedRiccatiSolver([(nx, nu, 0, nx, 0)] * N + [(nx, 0, 0, nx, 0)], nx, batch=128, device=0)
+    synth_device.fill_problems(s, seed=1234, mode="W")
+    prob = synth_device.download_problem(s, b)
+    s.close()
+    op = ora.Problem.from_knots(prob.stages, prob.G0, prob.g0)
+    osol = ora.ProximalRiccatiSolver(op)
+    osol.backward(1e-14)
+    ref = op.initialize_solution()
+    osol.forward(*ref)
+    scale = max(1.0, max(float(np.abs(v).max()) for v in ref[3]))
+    assert np.abs(out["xs"][0] - np.concatenate(ref[0])).max() <= 1e-9 * scale
+    assert np.abs(out["lbdas"][0] - np.concatenate(ref[3])).max() <= 1e-9 * scale
+
+
 def test_bench_two_ranks_on_one_gpu():
     """The N > 1 launch line of the driver (torch.distributed.run, one rank per GPU) with two ranks
     sharing this box's only GPU (gloo barrier): whole-job value = all ranks' sweeps / max time."""
     d = _bench_line(lambda port: ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                                   "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
-                                  "--steps", "2", "--warmup", "1", "--batch", "128", "--backend", "gloo", "--same-device"])
+                                  "--steps", "2", "--warmup", "1", "--batch", "128", "--backend", "gloo", "--same-device",
+                                  "--full"])
     assert d["n_gpus"] == 2 and "cpu_baseline" not in d and "parallel_in_time" not in d
     assert abs(d["value"] - 2 * 128 * 2 / (d["ms_per_step"] * 2e-3)) / d["value"] < 1e-6
 
@@ -551,7 +590,7 @@ def test_bench_gpus_2_spawns_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "128",
-                        "--backend", "gloo", "--same-device", "--single-generator"], cwd=root, env=env,
+                        "--backend", "gloo", "--same-device", "--single-generator", "--full"], cwd=root, env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     import json

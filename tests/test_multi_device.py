@@ -259,7 +259,7 @@ def test_gpu_bench_lines_for_eight_ranks_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     root = os.path.dirname(HERE)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--same-device", "--backend", "gloo", "--batch", "64",
-                        "--steps", "2", "--warmup", "1", "--single-generator", "--no-cpu", "--no-extras", "--pmc", "off"],
+                        "--steps", "2", "--warmup", "1", "--single-generator", "--no-cpu", "--no-extras", "--pmc", "off", "--full"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
