@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -214,6 +215,7 @@ struct gar_hip_solver {
   // hand-over knot per (problem, local leg)
   bool cseg_on = false;
   bool mu_divides = false; // some knot's solve divides by mueq outright (see gar_hip_backward_legs_async)
+  bool any_nc = false;     // some knot carries constraints: a non-finite mueq is refused (ibid.)
   gar::CsegKernels cseg;
   int *d_cseg_resume = nullptr;
   gar_hip_solver *flay = nullptr;
@@ -1658,12 +1660,18 @@ int gar_hip_backward_legs_async(gar_hip_solver *s, double mueq) {
   if (!s)
     return fail(GAR_HIP_ERR_ARG, "null solver");
   // A knot whose solve divides by mueq outright -- terminalSolve without controls, Z = C / mu (riccati-kernel.hxx:146-149);
-  // the decoupled constrained stage and the fold (gar_wave2.hpp, gar_fold.hpp: D = 0 makes kktMat singular at mu = 0, the
-  // reference throws there, :239-241) -- turns mueq = 0 (or a NaN) into infinities that the factorisations downstream
-  // index with: reported as the failed stage it is, before anything is launched
+  // the serial constrained chain and the constrained segment legs (gar_wave2.hpp's decoupled stage; both bind only where
+  // the terminal knot is constrained) -- turns mueq = 0 into infinities that the factorisations downstream index with:
+  // reported as the failed stage it is, before anything is launched.  The other fold solvers divide only on the device's
+  // say-so: the fold flags mu <= 0 and hands such a problem to the generic leg kernels (gar_fold.hpp), which solve
+  // [Rhat D^T; D 0] where D has full row rank and report the singular stages themselves, as the reference does
+  // (:239-241).  A non-finite mueq on constrained knots is refused whatever the family.
   if (s->mu_divides && !(std::fabs(mueq) >= 1e-290))
     return fail(GAR_HIP_ERR_FACTOR, "Failed stage LDL factorization (mueq = " + std::to_string(mueq) +
                                         " on constrained knots whose solve divides by it)");
+  if (s->any_nc && !(std::fabs(mueq) <= DBL_MAX))
+    return fail(GAR_HIP_ERR_FACTOR, "Failed stage LDL factorization (mueq = " + std::to_string(mueq) +
+                                        " on constrained knots)");
   GAR_MULTI(s, multi_backward_legs(s, mueq));
   s->eager_fwd = false;
   if (s->ev_pref) { // a read-back of the previous sweep's gains may still be in flight on the second stream
@@ -1700,7 +1708,8 @@ int gar_hip_set_option(const char *name, const char *value) {
     key = "GAR_HIP_" + key;
   static const char *known[] = {"BACKWARD", "WIDE", "LEG_WAVES", "CONDENSED", "CONDENSED_REDUCED", "CONDENSED_CR", "LEGS",
                                 "FOLD", "SEG_LEGS", "INIT", "FORCE_GENERIC", "PAD", "SPD_ACCEPT", "STAGE_NT", "EAGER",
-                                "MULTI_EXCHANGE", "PIPE_PRIORITY", "FORWARD", "PIPELINE"};
+                                "MULTI_EXCHANGE", "PIPE_PRIORITY", "FORWARD", "PIPELINE", "CSTR_SEG_LEGS",
+                                "CSTR_SEG_LEG_END", "CSTR_SEG_FORWARD"};
   bool ok = false;
   for (const char *k : known)
     ok |= key == std::string("GAR_HIP_") + k;

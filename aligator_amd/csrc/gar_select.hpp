@@ -432,10 +432,12 @@ int configure_padded_or_not(gar_hip_solver *s) {
     }
   }
   // (see gar_hip_backward_legs_async)
-  s->mu_divides = s->fold;
+  s->mu_divides = s->cseg_on;
+  s->any_nc = false;
   for (int t = 0; t <= s->horizon; ++t) {
     const int32_t *d = &s->dims5[5 * (size_t)t];
     s->mu_divides |= d[2] > 0 && (d[1] == 0 || s->wave_kernel != nullptr);
+    s->any_nc |= d[2] > 0;
   }
   return GAR_HIP_OK;
 }

@@ -116,3 +116,28 @@ def randomly_modify_problem(rng, prob: LqrProblem) -> None:
         kn.A += 0.1 * rng.standard_normal(kn.A.shape)
         kn.B += 0.1 * rng.standard_normal(kn.B.shape)
         kn.q += 0.1 * rng.standard_normal(kn.q.shape)
+
+
+MUEQ_KINDS = ("d0", "dfull", "alt", "mixed")
+
+
+def mueq_problem(kind: str, nx: int, nu: int, nc: int, horz: int, seed: int = 0) -> LqrProblem:
+    """The problems of the parity matrix over the proximal parameter mueq (tests/parity_cases.py,
+    tests/golden/make_mueq_golden.py): generator "W" with a dense random C on every constrained knot and
+      d0     D = 0 on every knot;
+      dfull  a random D on every knot;
+      alt    a random D on the odd knots;
+      mixed  constraints on two knots out of three with a random D, the terminal knot unconstrained."""
+    rng = np.random.default_rng([seed, nx, nu, nc, horz, MUEQ_KINDS.index(kind)])
+    knots = []
+    for t in range(horz + 1):
+        c = 0 if kind == "mixed" and (t == horz or t % 3 == 2) else nc
+        knots.append(generate_knot(rng, nx, nu if t < horz else 0, c, singular=t < horz, mode="W"))
+    for t, k in enumerate(knots):
+        k.C[...] = rng.uniform(-1, 1, k.C.shape)
+        if t < horz and (kind in ("dfull", "mixed") or (kind == "alt" and t % 2 == 1)):
+            k.D[...] = rng.uniform(-1, 1, k.D.shape)
+    prob = LqrProblem(knots, nx)
+    prob.G0[...] = -np.eye(nx)
+    prob.g0[...] = rng.standard_normal(nx)
+    return prob

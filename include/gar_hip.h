@@ -264,10 +264,13 @@ int gar_hip_update_lq_subproblem_device(gar_hip_solver *s, const double *deriv_d
 
 /* ---- the sweep ------------------------------------------------------------ */
 /* backward(mueq): returns 0, or GAR_HIP_ERR_FACTOR if any stage factorisation
- * of any problem failed (the reference throws).  mueq = 0 (|mueq| < 1e-290, NaN) on a problem with a knot whose
- * solve divides by it -- a constrained knot without controls, Z = C / mu (riccati-kernel.hxx:146-149); the
- * specialised constrained families -- is GAR_HIP_ERR_FACTOR before anything is launched (the reference: infinities,
- * or its "failed stage" exception on the singular [Rhat 0; 0 0]). */
+ * of any problem failed (the reference throws).  mueq = 0 (|mueq| < 1e-290) where a kernel divides by it outright --
+ * a constrained knot without controls, Z = C / mu (riccati-kernel.hxx:146-149); the serial constrained family and the
+ * constrained segment legs, which bind only where the terminal knot is constrained -- is GAR_HIP_ERR_FACTOR before
+ * anything is launched (the reference: infinities).  On the other leg-mode solvers with constrained knots the device
+ * hands such a problem to the generic leg kernels, which solve it where [Rhat D^T; D 0] is nonsingular and report the
+ * singular stages (the reference's "failed stage" exception, e.g. on [Rhat 0; 0 0] where D = 0) per problem.  A
+ * non-finite mueq on a problem with constrained knots is GAR_HIP_ERR_FACTOR up front on every family. */
 int gar_hip_backward(gar_hip_solver *s, double mueq);
 int gar_hip_backward_async(gar_hip_solver *s, double mueq);
 /* forward: theta (host, ntheta doubles per problem, batch-major) or NULL.

@@ -67,30 +67,33 @@ def compare_factors(hip_datas, ora_solver, N, tol, names=("ff", "fb", "fth"),
 CONDITIONING_MARGIN = 10.0   # x what three independent CPU solves of the same problem disagree by
 
 
-def check_serial(prob, mueq, tol, lib_path=None, theta=None, kkt_tol=None, factors=True, conditioned=False):
+def check_serial(prob, mueq, tol, lib_path=None, theta=None, kkt_tol=None, factors=True, conditioned=False,
+                 conditioned_factors=False):
     """conditioned (constrained problems with a small mu; theta = None): each part of the solution is held to
     max(tol, CONDITIONING_MARGIN x the disagreement of the oracle and LAPACK on the dense KKT matrix) -- see
-    conditioning_bound."""
+    conditioning_bound; conditioned_factors: the factors and kkt0 too, to the largest of those."""
     solver = ProximalRiccatiSolver(prob, lib_path=lib_path)
     assert solver.backward(mueq)
     sol = lqrInitializeSolution(prob)
     assert solver.forward(*sol, theta)
     _, osol, ref = oracle_serial(prob, mueq, theta)
     sc = scale_of(ref)
-    tols = [tol] * 4
+    tols, ftol = [tol] * 4, tol
     if conditioned and theta is None:
         bound, _ = conditioning_bound(prob, mueq, ref)
         tols = [max(tol, CONDITIONING_MARGIN * b) for b in bound]
+        if conditioned_factors:         # (the factors held like check_parallel's)
+            ftol = max(tols)
     for A, B, tl in zip(sol, ref, tols):
         assert maxdiff(A, B) <= tl * sc
     if kkt_tol is not None:
         assert max(lqrComputeKktError(prob, *sol, mueq=mueq, theta=theta)) <= kkt_tol
     if factors:
-        compare_factors(solver.datas, osol, prob.horizon, tol)
+        compare_factors(solver.datas, osol, prob.horizon, ftol)
         ff, fth, g, H = solver._impl.initial(0)
         for a, b in ((ff, osol.kkt0_ff), (fth, osol.kkt0_fth), (g, osol.thGrad), (H, osol.thHess)):
             if a.size:
-                assert np.abs(a - b).max() <= tol * max(1.0, np.abs(b).max())
+                assert np.abs(a - b).max() <= ftol * max(1.0, np.abs(b).max())
     return solver, sol, ref
 
 
@@ -98,10 +101,13 @@ def _rel(a, b):
     return np.abs(a - b).max() / max(1.0, np.abs(b).max()) if b.size else 0.0
 
 
-def check_dense(prob, mueq, tol, lib_path=None, theta=None, kkt_tol=None):
+def check_dense(prob, mueq, tol, lib_path=None, theta=None, kkt_tol=None, conditioned=False):
     """RiccatiSolverDense (tests/gar/riccati.cpp:141-155): the HIP stage-dense solver against its
     oracle (oracle/dense_riccati.py) -- trajectory, every stage's ff / fb / ft rows [K; Z; L; Y],
-    Pxx, px, Pxt, Ptt, pt, kkt0, thGrad, thHess -- and against the Riccati oracle's trajectory."""
+    Pxx, px, Pxt, Ptt, pt, kkt0, thGrad, thHess -- and against the Riccati oracle's trajectory.
+    conditioned (constrained problems with a small mu; theta = None): each part of the solution is held to
+    max(tol, CONDITIONING_MARGIN x conditioning_bound), the factors to the largest of those, and below mu = 1e-9 they
+    are not compared (as in check_parallel)."""
     solver = RiccatiSolverDense(prob, lib_path=lib_path)
     assert solver.kernel_name == "dense"
     assert solver.backward(mueq)
@@ -112,23 +118,32 @@ def check_dense(prob, mueq, tol, lib_path=None, theta=None, kkt_tol=None):
     ref = lqrInitializeSolution(prob)
     o.forward(*ref, theta)
     sc = scale_of(ref)
-    for A, B in zip(sol, ref):
-        assert maxdiff(A, B) <= tol * sc
+    tols, ftol = [tol] * 4, tol
     _, _, ric = oracle_serial(prob, mueq, theta)
-    for A, B in zip(sol, ric):
-        assert maxdiff(A, B) <= 10 * tol * sc
+    if conditioned and theta is None:
+        bound, _ = conditioning_bound(prob, mueq, ric)
+        tols = [max(tol, CONDITIONING_MARGIN * b) for b in bound]
+        # the gains of a coupled knot solve [Rhat D^T; D -mu I], conditioned like 1 / mu: two factorisations of it
+        # differ by ~ eps / mu (2e-12 at mu = 1e-4, 5e-8 at 1e-8 on the mueq matrix's problems)
+        ftol = max(max(tols), CONDITIONING_MARGIN * np.finfo(float).eps / mueq if mueq > 0 else 0.0)
+    for A, B, tl in zip(sol, ref, tols):
+        assert maxdiff(A, B) <= tl * sc
+    for A, B, tl in zip(sol, ric, tols):
+        assert maxdiff(A, B) <= 10 * tl * sc
     if kkt_tol is not None:
         assert max(lqrComputeKktError(prob, *sol, mueq=mueq, theta=theta)) <= kkt_tol
+    if conditioned and mueq <= 1e-9 and any(k.nc > 0 for k in prob.stages):
+        return solver, sol, ref
     for t in range(prob.horizon + 1):
         f, d = solver.datas[t], o.stage_factors[t]
         assert f.ff.shape == d.ff.shape and f.fb.shape == d.fb.shape and f.fth.shape == d.ft.shape
         for a, b in ((f.ff, d.ff), (f.fb, d.fb), (f.fth, d.ft), (f.vm.Vxx, o.Pxx[t]), (f.vm.vx, o.px[t]),
                      (f.vm.Vxt, o.Pxt[t]), (f.vm.Vtt, o.Ptt[t]), (f.vm.vt, o.pt[t])):
-            assert _rel(a, b) <= tol, t
+            assert _rel(a, b) <= ftol, t
         assert np.array_equal(solver.getFeedback(t), f.fb) and np.array_equal(solver.getFeedforward(t), f.ff)
     for a, b in ((solver.kkt0.ff, o.kkt0_ff), (solver.kkt0.fth, o.kkt0_fth), (solver.thGrad, o.thGrad),
                  (solver.thHess, o.thHess)):
-        assert _rel(a, b) <= tol
+        assert _rel(a, b) <= ftol
     return solver, sol, ref
 
 
@@ -198,6 +213,7 @@ def check_parallel(prob, mueq, nthreads, tol, lib_path=None, max_refine=10, roun
     # (stage factors of constrained problems below mu ~ 1e-9: two Bunch-Kaufman runs on the same reduced KKT matrix,
     # conditioned like 1/mu, differ block by block by more than the solution does -- the oracle and LAPACK do:
     # the solution-level checks above stand alone there, as in check_serial's `factors` switch of the soak)
+    par.checked_solution = sol                                           # (before collapseFeedback changes fb[0])
     if not (conditioned and mueq <= 1e-9 and any(k.nc > 0 for k in prob.stages)):
         compare_factors(par.datas, opar, prob.horizon, ftol)
         par.collapseFeedback()
@@ -653,3 +669,305 @@ def check_constrained_legs_fold(lib_path=None, shapes=((8, 4, 4, 11, 3, 1e-6), (
     mixed.g0[...] = rng.standard_normal(nx)
     par = check_parallel(mixed, 1e-6, 3, tol, lib_path, conditioned=True)
     assert par._impl.kernel_name.startswith(f"wave_leg<{nx},{nu}>+fold")
+
+
+# ---- the proximal parameter over its whole range ----------------------------------------------------------------------
+# SolverProxDDP calls backward(mu()) with mu from mu_init = 1e-2 down to mu_lower_bound = 1e-8 (solver-proxddp.hpp:117,
+# 186): every family against the reference's own rule at each mueq, on problems with D = 0, D != 0, D on alternate
+# knots, and (leg mode) constraints on some knots only with an unconstrained terminal knot.
+MUEQ_RANGE = (1.0, 1e-2, 1e-4, 1e-8, 1e-11, 1e-14, 0.0)
+MUEQ_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mueq", "mueq_range.npz")
+# |solution - exact| / max(1, |exact|) per part (x, u, v, lambda) against the fixture's 50-digit solution, per mueq:
+# stated bounds, 10 eps / mueq and no less than 1e-11 (the Riccati recursion carries Vxx += C^T C / mueq: cond(Vxx) ~ 1 / mueq
+# on these problems, whose terminal knot is constrained; at mueq = 0 only the problem with an unconstrained terminal
+# knot is solvable, and well conditioned).  The oracle itself meets them with a margin of 3 ... 100
+# (test_mueq_golden_fixture_pins_the_oracle).
+MUEQ_GOLDEN_TOL = {1.0: (1e-11,) * 4, 1e-2: (1e-11,) * 4, 1e-4: (3e-11,) * 4, 1e-8: (3e-7,) * 4, 1e-11: (3e-4,) * 4,
+                   1e-14: (3e-1,) * 4, 0.0: (1e-10,) * 4}
+
+
+def load_mueq_golden():
+    """{(kind, mueq): [xs, us, vs, lbdas]} of the fixture, after checking that synth still makes its problems."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "make_mueq_golden", os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_mueq_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    d = np.load(MUEQ_GOLDEN)
+    probs = gen.problems()
+    assert str(d["inputs_sha256"]) == gen.inputs_sha256(probs.values()), "synth.mueq_problem changed: regenerate"
+    from oracle import dense_kkt
+    out = {}
+    for kind, prob in probs.items():
+        for i, mueq in enumerate(d["mueqs"]):
+            if f"{kind}_{i}" in d:
+                out[(kind, float(mueq))] = list(dense_kkt.dense_solution_to_traj(prob, d[f"{kind}_{i}"]))
+    return tuple(int(v) for v in d["shape"]), out
+
+
+def golden_errors(sol, exact):
+    return [max([0.0] + [float(np.abs(a - b).max() / max(1.0, np.abs(b).max())) for a, b in zip(A, B) if b.size])
+            for A, B in zip(sol, exact)]
+
+
+def reference_solvable(prob, mueq):
+    """The reference's own verdict: its backward succeeds and leaves every factor and the solution finite (it throws on
+    a singular stage KKT matrix, riccati-kernel.hxx:239-241, and divides by mu where a constrained knot has no
+    controls, :146-149)."""
+    s = ora.ProximalRiccatiSolver(to_oracle(prob))
+    if not s.backward(mueq):
+        return False
+    sol = lqrInitializeSolution(prob)
+    if not s.forward(*sol):
+        return False
+    arrs = [v for part in sol for v in part]
+    for t in range(prob.horizon + 1):
+        d = s.datas(t)
+        arrs += [d.ff, d.fb, d.Vxx, d.vx]
+    return all(np.isfinite(a).all() for a in arrs)
+
+
+def assert_reported_failure(backward, mueq):
+    try:
+        ok = backward(mueq)
+    except RuntimeError as e:
+        assert "Failed stage LDL factorization" in str(e), str(e)
+        return
+    assert not ok, f"mueq = {mueq}: the library reports success where the reference fails"
+
+
+def _mueq_solver(prob, row, lib_path):
+    if row["mode"] == "serial":
+        return ProximalRiccatiSolver(prob, lib_path=lib_path)
+    if row["mode"] == "dense":
+        return RiccatiSolverDense(prob, lib_path=lib_path)
+    return ParallelRiccatiSolver(prob.copy(), row["legs"], lib_path=lib_path, devices=row.get("devices"))
+
+
+def _check_resolves(s, prob, tol=1e-8, mueq=1e-6):
+    """A reported failure must not poison the solver: the same object solves the same problem at mueq = 1e-6."""
+    assert s.backward(mueq)
+    sol = lqrInitializeSolution(prob)
+    assert s.forward(*sol)
+    _, _, ref = oracle_serial(prob, mueq)
+    bound, _ = conditioning_bound(prob, mueq, ref)
+    sc = scale_of(ref)
+    for A, B, b in zip(sol, ref, bound):
+        assert maxdiff(A, B) <= max(tol, CONDITIONING_MARGIN * b) * sc
+
+
+def check_mueq_case(prob, mueq, row, lib_path=None, tol=1e-9, exact=None):
+    """One (family, problem, mueq) cell.  Reference-solvable: solution, every stage's factors, kkt0 and the KKT error
+    against the oracle (conditioned tolerances where mueq <= 1e-8 on constrained problems), and against `exact` (the
+    fixture's 50-digit solution) at MUEQ_GOLDEN_TOL.  Otherwise: a reported failure, after which the same solver solves
+    the problem at mueq = 1e-6.  Returns (solved, the solver, the largest relative error against the oracle, the
+    largest against `exact` or None)."""
+    constrained = any(k.nc > 0 for k in prob.stages)
+    conditioned = constrained and mueq <= 1e-8
+    mode = row["mode"]
+    if not reference_solvable(prob, mueq):
+        s = _mueq_solver(prob, row, lib_path)
+        assert s.kernel_name == row["kernel"], (s.kernel_name, row["kernel"])
+        assert_reported_failure(s.backward, mueq)
+        _check_resolves(s, prob)
+        return False, s, None, None
+    if mode == "serial":
+        s, sol, ref = check_serial(prob, mueq, tol, lib_path, conditioned=conditioned, conditioned_factors=True,
+                                   factors=not (conditioned and mueq <= 1e-9))
+    elif mode == "dense":
+        s, sol, ref = check_dense(prob, mueq, tol, lib_path, conditioned=conditioned)
+    else:
+        s = check_parallel(prob, mueq, row["legs"], tol, lib_path, conditioned=conditioned, devices=row.get("devices"))
+        sol = s.checked_solution
+        _, _, ref = oracle_serial(prob, mueq)
+    assert s.kernel_name == row["kernel"], (s.kernel_name, row["kernel"])
+    sc = scale_of(ref)
+    if mode != "parallel":          # (check_parallel holds the KKT error to the same bound)
+        okkt = max(lqrComputeKktError(prob, *ref, mueq=mueq)) / sc
+        kkt = max(lqrComputeKktError(prob, *sol, mueq=mueq)) / sc
+        assert kkt <= (max(tol, CONDITIONING_MARGIN * okkt) if conditioned else tol), (kkt, okkt)
+    err = max(maxdiff(A, B) for A, B in zip(sol, ref)) / sc
+    gerr = None
+    if exact is not None:
+        errs = golden_errors(sol, exact)
+        for part, (e, tl) in enumerate(zip(errs, MUEQ_GOLDEN_TOL[mueq])):
+            assert e <= tl, (row["name"], mueq, part, errs)
+        gerr = max(errs)
+    return True, s, err, gerr
+
+
+def check_mueq_row(row, lib_path=None, golden=None, mueqs=MUEQ_RANGE, report=None):
+    """One family (`row`: name, mode serial | dense | parallel, legs, devices, env (GAR_HIP_* switches), shape
+    (nx, nu, nc, N), kinds, kernel, chain) over `mueqs` and its problem kinds.  chain: which of the constrained stage
+    counters (constrained_bk_stages: d decoupled, c coupled, b Bunch-Kaufman) must be non-zero over the row.  golden: the
+    fixture (load_mueq_golden()), used where the row's shape is the fixture's.  Non-finite mueq is a reported failure
+    on the first kind."""
+    old = {k: os.environ.get(k) for k in row.get("env", {})}
+    os.environ.update(row.get("env", {}))
+    nx, nu, nc, N = row["shape"]
+    counts = [0, 0, 0]
+    solved = 0
+    try:
+        for ki, kind in enumerate(row["kinds"]):
+            prob = synth.mueq_problem(kind, nx, nu, nc, N)
+            for mueq in mueqs:
+                exact = None
+                if golden is not None and golden[0] == row["shape"]:
+                    exact = golden[1].get((kind, mueq))
+                    if exact is None:
+                        assert not reference_solvable(prob, mueq), ("fixture lacks a solvable pair", kind, mueq)
+                try:
+                    ok, s, err, gerr = check_mueq_case(prob, mueq, row, lib_path, exact=exact)
+                except AssertionError as e:
+                    raise AssertionError(f"{row['name']} {kind} mueq={mueq:g}: {e!r}") from e
+                solved += ok
+                if ok and row.get("chain"):
+                    coupled, bk = s._impl.constrained_bk_stages()
+                    counts[1] += coupled
+                    counts[2] += bk
+                    counts[0] += sum(k.nc > 0 for k in prob.stages[:N]) - coupled - bk
+                if report is not None and ok:
+                    r = report.setdefault((row["name"], mueq), [0.0, None])
+                    r[0] = max(r[0], err)
+                    if gerr is not None:
+                        r[1] = max(r[1] or 0.0, gerr)
+            if ki == 0:
+                s = _mueq_solver(prob, row, lib_path)
+                for bad in (float("nan"), float("inf"), float("-inf")):
+                    assert_reported_failure(s.backward, bad)
+                _check_resolves(s, prob)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    assert solved > 0
+    want = [c in row.get("chain", "") for c in "dcb"]
+    assert all(n > 0 for n, w in zip(counts, want) if w), ("the row does not reach the chain's stage kernels "
+                                                           "(decoupled, coupled, Bunch-Kaufman)", counts, row["chain"])
+    return counts
+
+
+def check_mueq_batch_of_four(lib_path=None, shape=(8, 4, 4, 5), legs=3):
+    """mueq = 0 on one fold solver: two problems the reference solves (D of full row rank, terminal knot unconstrained)
+    and two it cannot (D = 0: [Rhat 0; 0 0] is singular) -- exactly two failures, and the solver goes on."""
+    nx, nu, nc, N = shape
+    good = [synth.mueq_problem("mixed", nx, nu, nc, N, seed=s) for s in (0, 1)]
+    bad = [p.copy() for p in good]
+    for p in bad:
+        for k in p.stages:
+            k.D[...] = 0.0
+    probs = [good[0], bad[0], good[1], bad[1]]
+    assert [reference_solvable(p, 0.0) for p in probs] == [True, False, True, False]
+    s = BatchedRiccatiSolver([k.dims for k in probs[0].stages], probs[0].nc0, batch=4, num_legs=legs, lib_path=lib_path)
+    assert s.kernel_name == f"wave_leg<{nx},{nu}>+fold"
+    s.upload(probs)
+    assert_reported_failure(s.backward, 0.0)
+    assert s.num_failed() == 2
+    for mueq in (1e-6, 0.0):
+        s.upload(probs if mueq else [good[0], good[1], good[0], good[1]])
+        assert s.backward(mueq) and s.forward() and s.num_failed() == 0
+        for b in range(4):
+            p = probs[b] if mueq else good[b % 2]
+            _, _, ref = oracle_serial(p, mueq)
+            bound, _ = conditioning_bound(p, mueq, ref)
+            sc = scale_of(ref)
+            for A, B, bd in zip(s.solution(b), ref, bound):
+                assert maxdiff(A, B) <= max(1e-8, CONDITIONING_MARGIN * bd) * sc, (mueq, b)
+
+
+def check_mueq_unconstrained_bitwise(kernel, nx, nu, N, legs=1, env=None, lib_path=None):
+    """Without constraints mueq enters nothing: the results at 0, 1e-8 and 1 are the same bits."""
+    old = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
+    try:
+        prob = synth.generate_lq_problem(5, np.ones(nx), N, nx, nu, mode="W")
+        s = BatchedRiccatiSolver([k.dims for k in prob.stages], prob.nc0, batch=1, num_legs=legs, lib_path=lib_path)
+        assert s.kernel_name == kernel, s.kernel_name
+        s.upload([prob])
+        runs = []
+        for mueq in (0.0, 1e-8, 1.0):
+            assert s.backward(mueq) and s.forward()
+            f = [s.factor(t, 0) for t in range(N + 1)]
+            runs.append([np.concatenate([np.ravel(v) for v in part]) for part in s.solution(0)] +
+                        [np.concatenate([np.ravel(a) for x in f for a in (x.ff, x.fb, x.vm.Vxx, x.vm.vx)])])
+        for other in runs[1:]:
+            for a, b in zip(runs[0], other):
+                assert np.array_equal(a, b)
+        _, _, ref = oracle_serial(prob, 0.0)
+        for A, B in zip(s.solution(0), ref):
+            assert maxdiff(A, B) <= 1e-9 * scale_of(ref)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _row(name, mode, shape, kinds, kernel, legs=1, env=None, devices=None, chain=""):
+    return dict(name=name, mode=mode, shape=shape, kinds=kinds, kernel=kernel, legs=legs, env=env or {},
+                devices=devices, chain=chain)
+
+
+ALL_KINDS, UNIFORM_KINDS = ("d0", "dfull", "alt", "mixed"), ("d0", "dfull", "alt")
+# The matrix's families at small shapes (the emulator's and the GPU's): name -> row.  Each row asserts its kernel_name.
+MUEQ_ROWS = [
+    _row("serial_generic", "serial", (10, 5, 3, 5), ALL_KINDS, "generic"),
+    _row("serial_forced_generic", "serial", (8, 4, 4, 5), ALL_KINDS, "generic", env={"GAR_HIP_FORCE_GENERIC": "1"}),
+    _row("wave_8_4_4", "serial", (8, 4, 4, 5), UNIFORM_KINDS, "wave<8,4,4>", chain="dcb"),
+    _row("wave_16_8_8", "serial", (16, 8, 8, 3), UNIFORM_KINDS, "wave<16,8,8>", chain="dcb"),
+    _row("wave_36_12_32", "serial", (36, 12, 32, 2), UNIFORM_KINDS, "wave<36,12,32>", chain="dc"),
+    _row("dense", "dense", (8, 4, 4, 5), ALL_KINDS, "dense"),
+    _row("fold", "parallel", (8, 4, 4, 5), ("d0",), "wave_leg<8,4>+fold|wave_seg<8,4,4>", legs=3),
+    _row("cstr_seg", "parallel", (8, 4, 4, 5), ("dfull", "alt"), "wave_leg<8,4>+fold|wave_seg<8,4,4>", legs=3,
+         chain="dcb"),
+    _row("cstr_seg_16", "parallel", (16, 8, 8, 5), ("dfull", "alt"), "wave_leg<16,8>+fold|wave_seg<16,8,8>", legs=2,
+         chain="dcb"),
+    _row("cstr_seg_leg_end0", "parallel", (8, 4, 4, 5), ("dfull",), "wave_leg<8,4>+fold|wave_seg<8,4,4>", legs=3,
+         env={"GAR_HIP_CSTR_SEG_LEG_END": "0"}),
+    _row("cstr_seg_fwd_generic", "parallel", (8, 4, 4, 5), ("dfull",), "wave_leg<8,4>+fold|wave_seg<8,4,4>", legs=3,
+         env={"GAR_HIP_CSTR_SEG_FORWARD": "generic"}),
+    _row("fold_to_generic", "parallel", (8, 4, 4, 5), ("dfull", "alt", "mixed"), "wave_leg<8,4>+fold", legs=3,
+         env={"GAR_HIP_CSTR_SEG_LEGS": "0"}),
+    _row("fold_mixed_12_8_3", "parallel", (12, 8, 3, 11), ("mixed",), "wave_leg<12,8>+fold", legs=3),
+    _row("generic_legs", "parallel", (8, 4, 4, 5), ALL_KINDS, "generic", legs=3, env={"GAR_HIP_FOLD": "0"}),
+    _row("generic_legs_12_8_3", "parallel", (12, 8, 3, 11), ("mixed",), "generic", legs=3, env={"GAR_HIP_FOLD": "0"}),
+    _row("two_subsolvers_fold", "parallel", (8, 4, 4, 5), ("d0",), "wave_leg<8,4>+fold|wave_seg<8,4,4>", legs=3,
+         devices=[0, 0]),
+    _row("two_subsolvers_cstr_seg", "parallel", (8, 4, 4, 5), ("dfull",), "wave_leg<8,4>+fold|wave_seg<8,4,4>",
+         legs=3, devices=[0, 0]),
+]
+
+
+def check_mueq_bench_shape(kind, mueq, legs, nx=36, nu=12, nc=32, N=256, lib_path=None):
+    """The benchmark's shape (bench/gar-riccati.cpp: N = 256, nx = 36, nu = 12, nc = 32) at one mueq, serial (legs = 1)
+    or in leg mode.  Neither the 50-digit reference nor the dense LAPACK solve scales to N = 256: each part of the solution
+    is held to max(1e-9, CONDITIONING_MARGIN x the disagreement of the oracle's serial and leg-parallel solvers), the KKT
+    error to max(1e-9, CONDITIONING_MARGIN x the larger of the oracle's two).  Returns the largest relative error."""
+    prob = synth.mueq_problem(kind, nx, nu, nc, N)
+    _, _, ref = oracle_serial(prob, mueq)
+    opar = ora.ParallelRiccatiSolver(to_oracle(prob), max(legs, 32))
+    assert opar.backward(mueq)
+    leg = lqrInitializeSolution(prob)
+    opar.forward(*leg)
+    sc = scale_of(ref)
+    tols = [max(1e-9, CONDITIONING_MARGIN * maxdiff(a, b) / sc) for a, b in zip(leg, ref)]
+    okkt = max(max(lqrComputeKktError(prob, *o, mueq=mueq)) for o in (ref, leg)) / sc
+    if legs == 1:
+        s = ProximalRiccatiSolver(prob, lib_path=lib_path)
+        assert s.kernel_name == f"wave<{nx},{nu},{nc}>", s.kernel_name
+    else:
+        s = ParallelRiccatiSolver(prob.copy(), legs, lib_path=lib_path)
+        assert s.kernel_name == f"wave_leg<{nx},{nu}>+fold|wave_seg<{nx},{nu},{nc}>", s.kernel_name
+    assert s.backward(mueq)
+    sol = lqrInitializeSolution(prob)
+    assert s.forward(*sol)
+    if kind != "d0":
+        assert sum(s._impl.constrained_bk_stages()) > 0
+    errs = [maxdiff(a, b) / sc for a, b in zip(sol, ref)]
+    assert all(e <= t for e, t in zip(errs, tols)), (errs, tols)
+    kkt = max(lqrComputeKktError(prob, *sol, mueq=mueq)) / sc
+    assert kkt <= max(1e-9, CONDITIONING_MARGIN * okkt), (kkt, okkt)
+    return max(errs)

@@ -86,3 +86,28 @@ def test_product_never_imports_oracle():
                 if f.endswith((".py", ".cpp", ".hpp", ".h", ".hip")):
                     txt = open(os.path.join(dp, f)).read()
                     assert not re.search(r"^\s*(from|import)\s+oracle|gar_oracle|libgar_oracle", txt, re.M), f
+
+
+def _documented_switches():
+    src = open(HEADER).read()
+    block = src[src.index("/* Behaviour switches."):src.index("int gar_hip_set_option(")]
+    # a switch: NAME = value, at the start of a list line or after one of | , ; (not "G0 = +-I" inside a note)
+    return sorted(set(re.findall(r"(?:^\s*\*\s+|[|,;]\s*)([A-Z][A-Z0-9_]*[A-Z0-9])\s*=", block, re.M)))
+
+
+def test_every_documented_switch_is_accepted(lib):
+    """gar_hip_set_option accepts every switch gar_hip.h lists (with and without the GAR_HIP_ prefix) and refuses
+    a name that is none of them; pure host logic."""
+    from aligator_amd.gar import get_option, set_option
+    names = _documented_switches()
+    assert len(names) >= 20 and {"CSTR_SEG_LEGS", "CSTR_SEG_LEG_END", "CSTR_SEG_FORWARD", "PIPELINE"} <= set(names)
+    for name in names:
+        for key in (name, "GAR_HIP_" + name):
+            try:
+                set_option(key, "x")
+                assert get_option(name) == "x", key
+            finally:
+                set_option(key, None)
+    for bad in ("NO_SUCH_SWITCH", "GAR_HIP_NO_SUCH_SWITCH", "CSTR_SEG"):
+        with pytest.raises(ValueError, match="unknown switch"):
+            set_option(bad, "1")

@@ -1038,3 +1038,45 @@ def test_behaviour_switches_through_the_api():
         set_option("BACKWARD", None, EMU)
         set_option("FORCE_GENERIC", None, EMU)
     assert kernel()[0] == base
+
+
+# ---- mueq from 0 to 1: every family against the reference's own rule (tests/parity_cases.py, MUEQ_ROWS) ----------------
+@pytest.fixture(scope="module")
+def mueq_golden():
+    return pc.load_mueq_golden()
+
+
+@pytest.mark.parametrize("row", pc.MUEQ_ROWS, ids=[r["name"] for r in pc.MUEQ_ROWS])
+def test_mueq_range_parity(row, mueq_golden):
+    pc.check_mueq_row(row, EMU, golden=mueq_golden)
+
+
+def test_mueq_zero_batch_of_four_on_one_fold_solver():
+    pc.check_mueq_batch_of_four(EMU)
+
+
+@pytest.mark.parametrize("kernel,nx,nu,N,legs,env", [("wave<36,12>", 36, 12, 3, 1, {"GAR_HIP_BACKWARD": "wave"}),
+                                                     ("wave_leg<36,12>", 36, 12, 5, 2, None),
+                                                     ("generic", 8, 4, 5, 1, {"GAR_HIP_FORCE_GENERIC": "1"})])
+def test_mueq_has_no_effect_without_constraints(kernel, nx, nu, N, legs, env):
+    pc.check_mueq_unconstrained_bitwise(kernel, nx, nu, N, legs, env, EMU)
+
+
+def test_mueq_golden_fixture_pins_the_oracle(mueq_golden):
+    """The fixture's tolerances are achievable: the oracle (serial and leg-parallel) meets them on every solvable pair,
+    and the fixture holds every pair the reference solves."""
+    from oracle import oracle as ora
+    (nx, nu, nc, N), exact = mueq_golden
+    for kind in synth.MUEQ_KINDS:
+        prob = synth.mueq_problem(kind, nx, nu, nc, N)
+        for mueq in pc.MUEQ_RANGE:
+            if not pc.reference_solvable(prob, mueq):
+                continue
+            _, _, ref = pc.oracle_serial(prob, mueq)
+            opar = ora.ParallelRiccatiSolver(pc.to_oracle(prob), 3)
+            assert opar.backward(mueq)
+            leg = pc.lqrInitializeSolution(prob)
+            opar.forward(*leg)
+            for sol in (ref, leg):
+                errs = pc.golden_errors(sol, exact[(kind, mueq)])
+                assert all(e <= t for e, t in zip(errs, pc.MUEQ_GOLDEN_TOL[mueq])), (kind, mueq, errs)

@@ -779,3 +779,36 @@ def test_config4_talos_lq_shape():
             ParallelRiccatiSolver(prob.copy(), 5)
     finally:
         del os.environ["GAR_HIP_SEG_LEGS"]
+
+
+# ---- mueq from 0 to 1: every family against the reference's own rule (tests/parity_cases.py, MUEQ_ROWS) ----------------
+@pytest.fixture(scope="module")
+def mueq_golden():
+    return pc.load_mueq_golden()
+
+
+@pytest.mark.parametrize("row", pc.MUEQ_ROWS, ids=[r["name"] for r in pc.MUEQ_ROWS])
+def test_gpu_mueq_range_parity(row, mueq_golden):
+    report = {}
+    pc.check_mueq_row(row, golden=mueq_golden, report=report)
+    for (name, mueq), (err, gerr) in report.items():
+        print(f"mueq-report {name} {mueq:g} oracle {err:.2e} exact {'-' if gerr is None else f'{gerr:.2e}'}")
+
+
+def test_gpu_mueq_zero_batch_of_four_on_one_fold_solver():
+    pc.check_mueq_batch_of_four()
+
+
+@pytest.mark.parametrize("kernel,nx,nu,N,legs,env", [("wave<36,12>", 36, 12, 16, 1, {"GAR_HIP_BACKWARD": "wave"}),
+                                                     ("wave_leg<36,12>", 36, 12, 31, 4, None),
+                                                     ("generic", 8, 4, 9, 1, {"GAR_HIP_FORCE_GENERIC": "1"})])
+def test_gpu_mueq_has_no_effect_without_constraints(kernel, nx, nu, N, legs, env):
+    pc.check_mueq_unconstrained_bitwise(kernel, nx, nu, N, legs, env)
+
+
+@pytest.mark.parametrize("legs", [1, 32])
+@pytest.mark.parametrize("kind", ["d0", "dfull"])
+def test_gpu_mueq_range_on_the_bench_shape(kind, legs):
+    for mueq in (1e-2, 1e-8, 1e-11):
+        err = pc.check_mueq_bench_shape(kind, mueq, legs)
+        print(f"mueq-report bench_shape_{kind}_legs{legs} {mueq:g} oracle {err:.2e} exact -")
