@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(64, 1) gar_cseg_backward(MfmaParams P, int num
   using M = MfmaCfg<NX, NU, NC>;
   static_assert(NC > 0 && !M::WIDE, "the constrained one-wave family");
   constexpr int PK = C::PK;
-  constexpr bool QP = GAR_QR_PACKED != 0;
+  constexpr bool QP = true;
   const int lane = (int)threadIdx.x & 63;
   const int leg = (int)blockIdx.x + leg_begin, b = (int)blockIdx.y;
   if (only[b] != 1)
@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(64, 1) gar_cseg_backward(MfmaParams P, int num
     const double *rn = fac + (long long)(tstart + 1) * P.fac_rec;
     for (int e = lane; e < NX * NX; e += 64) {
       const int j = e / NX, i = e - j * NX;
-      V[i * PK + j] = rn[M::fVxx + gar_sym_index(GAR_VXX_PACKED, NX, i, j)];
+      V[i * PK + j] = rn[M::fVxx + gar_sym_index(1, NX, i, j)];
     }
     if (lane < NX)
       vn[lane] = rn[M::fvx + lane];
@@ -137,9 +137,7 @@ __global__ void __launch_bounds__(64, 1) gar_cseg_backward(MfmaParams P, int num
       for (int k = 0; k < NC; ++k)
         v = __builtin_fma(rec[M::tC + i * NC + k], rec[M::tC + j * NC + k] / P.mueq, v);
       V[i * PK + j] = v;
-      if (!GAR_VXX_PACKED)
-        out[M::tVxx + e] = v;
-      else if (i >= j)
+      if (i >= j)
         out[M::tVxx + gar_sym_index(1, NX, i, j)] = v;
     }
     if (lane < NX) {
@@ -170,7 +168,7 @@ __global__ void __launch_bounds__(64, 1) gar_cseg_backward(MfmaParams P, int num
     if constexpr (PHASE == 2) {
       if (lane == 0)
         atomicAdd(&P.slow[3], 1); // (gar_hip_constrained_bk_stages, as the serial chain counts)
-      wave_stage<NX, NU, 0, 0, NC, GAR_VXX_PACKED != 0>(P, sm, prob, fac, t, lane, L, S, failed, tracing);
+      wave_stage<NX, NU, 0, 0, NC, true>(P, sm, prob, fac, t, lane, L, S, failed, tracing);
       if (flags & CSEG_SINGLE) { // (its Vxx, vx are complete in the record: this stage flushes its own)
         if (lane == 0) {
           P.resume[unit] = t - 1 >= t_beg ? t - 1 : -1;
@@ -182,13 +180,11 @@ __global__ void __launch_bounds__(64, 1) gar_cseg_backward(MfmaParams P, int num
     } else {
       if (PHASE == 1 && lane == 0)
         atomicAdd(&P.slow[2], 1);
-      // (the lane offsets re-derived per stage: gar_backward_wave_body, GAR_COUPLED_REFRESH_LANE / GAR_CSTR_REFRESH_LANE)
-      constexpr bool REFRESH = PHASE == 1 ? (GAR_COUPLED_REFRESH_LANE != 0) : (GAR_CSTR_REFRESH_LANE != 0);
-      const int lane_t = REFRESH ? lane + fence0(S.fi) : lane;
+      // (the lane offsets re-derived per stage: gar_backward_wave_body)
+      const int lane_t = lane + fence0(S.fi);
       WaveLane<NX, NU, NC> Lt;
-      if constexpr (REFRESH)
-        wave_lane_init<NX, NU, NC, QP>(Lt, lane_t);
-      if (!wave_stage2<NX, NU, NC, PHASE == 1>(P, sm, prob, fac, t, lane_t, REFRESH ? Lt : L, S, failed, vflush, tracing)) {
+      wave_lane_init<NX, NU, NC, QP>(Lt, lane_t);
+      if (!wave_stage2<NX, NU, NC, PHASE == 1>(P, sm, prob, fac, t, lane_t, Lt, S, failed, vflush, tracing)) {
         if (lane == 0) { // over to the next kernel of the chain from this knot on
           P.resume[unit] = t;
           if (PHASE == 1)
@@ -207,18 +203,13 @@ __global__ void __launch_bounds__(64, 1) gar_cseg_backward(MfmaParams P, int num
   if constexpr (PHASE < 2) {
     if (lane == 0)
       P.resume[unit] = (PHASE == 1 && (flags & CSEG_SINGLE) && tstart >= t_beg) ? -2 - tstart : -1;
-    wave_flush_vxx<NX, GAR_VXX_PACKED != 0, PK>(V, vflush, lane);
+    wave_flush_vxx<NX, true, PK>(V, vflush, lane);
   }
   if (failed && lane == 0)
     atomicOr(&P.status[b], failed);
 }
 
-#ifndef GAR_CSEG_BK_BLOCKED
-#define GAR_CSEG_BK_BLOCKED 1
-#endif
-#ifndef GAR_CSEG_STAGE_THREADS
 #define GAR_CSEG_STAGE_THREADS 512
-#endif
 // ---- (1b) the leg-END stage of every non-final leg, one workgroup per (leg, problem) ---------------------------------
 // Behind a leg end V' = 0: the stage is [kff K; zff Z] = -M^-1 [r S^T; d C] with M = [R D^T; D -mu I] of the knot's own
 // blocks (:151-172), yff = f + B kff, Aff = A + B K, Vxx = Q + S K + C^T Z, vx = q + S kff + C^T zff (:175-183) -- no
@@ -272,7 +263,7 @@ __global__ void __launch_bounds__(GAR_CSEG_STAGE_THREADS) gar_cseg_leg_end(MfmaP
     const int a = i >= j ? i : j, c = i >= j ? j : i;
     double v;
     if (a < NU)
-      v = GAR_QR_PACKED ? knot[M::kR + gar_lower_index(NU, a, c)] : knot[M::kR + c * NU + a];
+      v = knot[M::kR + gar_lower_index(NU, a, c)];
     else if (c < NU)
       v = knot[M::kD + c * NC + (a - NU)];
     else
@@ -297,7 +288,7 @@ __global__ void __launch_bounds__(GAR_CSEG_STAGE_THREADS) gar_cseg_leg_end(MfmaP
   for (int e = w.tid; e < bs; e += w.nthr) {
     const int j = e / NX, i = e - j * NX;
     Am[e] = knot[M::kA + e];
-    Qm[e] = GAR_QR_PACKED ? knot[M::kQ + (i >= j ? gar_lower_index(NX, i, j) : gar_lower_index(NX, j, i))] : knot[M::kQ + e];
+    Qm[e] = knot[M::kQ + (i >= j ? gar_lower_index(NX, i, j) : gar_lower_index(NX, j, i))];
   }
   for (int e = w.tid; e < NX; e += w.nthr) {
     qv[e] = knot[M::kq + e];
@@ -305,7 +296,7 @@ __global__ void __launch_bounds__(GAR_CSEG_STAGE_THREADS) gar_cseg_leg_end(MfmaP
   }
   __syncthreads();
   int failed;
-  if constexpr (GAR_CSEG_BK_BLOCKED != 0 && NK >= 24)
+  if constexpr (NK >= 24)
     failed = wg_bk_factor_blocked(w, NK, Mk, NK, sub, piv, ctrl, wk);
   else
     failed = wg_bk_factor(w, NK, Mk, NK, sub, piv, ctrl);
@@ -340,7 +331,7 @@ __global__ void __launch_bounds__(GAR_CSEG_STAGE_THREADS) gar_cseg_leg_end(MfmaP
   for (int e = w.tid; e < bs; e += w.nthr) {
     const int j = e / NX, i = e - j * NX;
     if (i >= j)
-      out[M::fVxx + gar_sym_index(GAR_VXX_PACKED, NX, i, j)] = Qm[e];
+      out[M::fVxx + gar_sym_index(1, NX, i, j)] = Qm[e];
   }
   for (int e = w.tid; e < NX; e += w.nthr)
     out[M::fvx + e] = vx[e];
@@ -353,9 +344,7 @@ __global__ void __launch_bounds__(GAR_CSEG_STAGE_THREADS) gar_cseg_leg_end(MfmaP
 
 // ---- (2) the parameter part -------------------------------------------------------------------------------------------
 
-#ifndef GAR_CSEG_CHAIN_THREADS
 #define GAR_CSEG_CHAIN_THREADS 576
-#endif
 template <int NX> __host__ __device__ constexpr int cseg_chain_lds_doubles() { return 3 * NX * NX + 16; }
 
 // (2a) the chain Vxt_t = Aff_t^T Vxt_{t+1} (:305-306; at the leg end Aff^T I, :186), Vxt of every stage written to its
@@ -451,7 +440,7 @@ __global__ void __launch_bounds__(GAR_CSEG_STAGE_THREADS) gar_cseg_param_stage(C
   const bool leg_end = !last_leg && (t == t_end - 1);
   auto vxx_src = [&](const double *rec_vxx, int e) { // full symmetric block from the packed lower triangle
     const int j = e / NX, i = e - j * NX;
-    return rec_vxx[gar_sym_index(GAR_VXX_PACKED, NX, i, j)];
+    return rec_vxx[gar_sym_index(1, NX, i, j)];
   };
   if (t == N) { // the terminal knot (nu = 0): ff, fb row-major already; Vxx packed
     const gar_factor_offsets fo = gar_factor_layout(NX, 0, NC, m.nx2, 0);
@@ -497,7 +486,7 @@ __global__ void __launch_bounds__(GAR_CSEG_STAGE_THREADS) gar_cseg_param_stage(C
     const int a = i >= j ? i : j, c = i >= j ? j : i; // a >= c
     double v;
     if (a < NU)
-      v = GAR_QR_PACKED ? knot[M::kR + gar_lower_index(NU, a, c)] : knot[M::kR + c * NU + a];
+      v = knot[M::kR + gar_lower_index(NU, a, c)];
     else if (c < NU)
       v = knot[M::kD + c * NC + (a - NU)];
     else
@@ -532,7 +521,7 @@ __global__ void __launch_bounds__(GAR_CSEG_STAGE_THREADS) gar_cseg_param_stage(C
   // (from 24 columns on in its panel-blocked form, as the any-dimension stage kernel does: one wave runs the pivot search,
   // the trailing matrix is updated once per panel on MFMA tiles -- bunchkaufman.hpp:172-344 is the reference's own)
   int failed;
-  if constexpr (GAR_CSEG_BK_BLOCKED != 0 && NK >= 24)
+  if constexpr (NK >= 24)
     failed = wg_bk_factor_blocked(w, NK, Mk, NK, sub, piv, ctrl, wk);
   else
     failed = wg_bk_factor(w, NK, Mk, NK, sub, piv, ctrl);

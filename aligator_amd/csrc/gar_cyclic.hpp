@@ -111,14 +111,11 @@ template <int NX> struct CyclicLds {
 // Round 6: blocks wider than one DPP row (36, 32) are factorised in panels of 12 / 16 columns with the trailing
 // matrix updated on MFMA tiles (gar_ldl_blocked.hpp; 630 v_readlane broadcast-FMA pairs at NX = 36 otherwise): L goes
 // straight to LDS where the blocked inverse wants it.  Dm is consumed.
-#ifndef GAR_CYC_BLOCKED_LDL
-#define GAR_CYC_BLOCKED_LDL 1
-#endif
 template <int NX>
 __device__ __forceinline__ int cyc_inverse(double *sm, int lane) {
   using L = CyclicLds<NX>;
   double *Dm = sm + L::oD, *Wm = sm + L::oW, *Mm = sm + L::oM, *Tm = sm + L::oT, *Dl = sm + L::oDl;
-  if constexpr (GAR_CYC_BLOCKED_LDL && NX > 16 && (CondCfg<NX>::BS == 12 || CondCfg<NX>::BS == 16)) {
+  if constexpr (NX > 16 && (CondCfg<NX>::BS == 12 || CondCfg<NX>::BS == 16)) {
     for (int e = lane; e < NX * NX; e += 64) { // unit diagonal, zeros above it: the strictly lower part is the routine's
       const int j = e / NX, i = e - j * NX;
       if (i <= j)

@@ -1282,9 +1282,7 @@ __device__ inline void wg_bk_solve_mfma_impl(const WG &w, int n, const double *a
 }
 // X(i, c) at x[i xrs + c xcs]: one of the strides is 1 at every call site (column-major or row-major X); the two
 // layouts are compiled separately so that the unit stride folds into the instructions' immediate offsets
-#ifndef GAR_SOLVE_NB
 #define GAR_SOLVE_NB 8
-#endif
 template <int MODE, int NB = GAR_SOLVE_NB>
 __device__ inline void wg_bk_solve_mfma(const WG &w, int n, const double *a, int lda, const double *subdiag,
                                         const int *piv, double *x, int xrs, int xcs, int ncols) {

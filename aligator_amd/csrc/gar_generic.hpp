@@ -142,9 +142,7 @@ __device__ inline int initial_stage(const WG &w, const GenericParams &P, int b, 
 // backward
 // ---------------------------------------------------------------------------
 // (GAR_BACKWARD_THREADS threads per (leg, problem): copies, product tiles and substitution strips spread over 16 waves)
-#ifndef GAR_BACKWARD_THREADS
 #define GAR_BACKWARD_THREADS 1024
-#endif
 __global__ void __launch_bounds__(GAR_BACKWARD_THREADS) gar_backward_generic(GenericParams P) {
   const WG w = wg_self();
   double *sm = gar_smem;
@@ -995,9 +993,7 @@ __device__ __forceinline__ const double *cond_tuple(const CondensedParams &P, in
 // ---------------------------------------------------------------------------------------------------------------
 // (GAR_CONDENSED_THREADS threads: 16 waves share the copies, the tiles of the products and the strips of the
 // substitutions; the panel factorisation stays one wave's work)
-#ifndef GAR_CONDENSED_THREADS
 #define GAR_CONDENSED_THREADS 1024
-#endif
 __device__ __forceinline__ double gar_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
 __device__ __forceinline__ void gar_atomic_max_nonneg(double *addr, double v) { // v >= 0 (or NaN -> +inf)
   if (!(v == v))

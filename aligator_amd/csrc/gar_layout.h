@@ -104,10 +104,6 @@ GAR_HD static inline gar_knot_offsets gar_knot_layout(int nx, int nu, int nc, in
 // c holding column c's rows c .. nx-1 followed by column nx-1-c's rows nx-1-c .. nx-1 (nx even).  The rest of the
 // block is not touched: the sweep writes, and the roll-out reads, 5.3 KB instead of 10.4 KB per stage at nx = 36.
 // Every other family stores the full column-major matrix.  gar_hip_get_value unpacks.
-// (-DGAR_VXX_PACKED=0 builds the library with full blocks everywhere: the A/B of scripts/ab_vxx_packed.sh)
-#ifndef GAR_VXX_PACKED
-#define GAR_VXX_PACKED 1
-#endif
 //   element (i, j) of the block, either order:
 GAR_HD static inline int gar_sym_index(int packed, int n, int i, int j) {
   if (!packed)
@@ -126,10 +122,6 @@ GAR_HD static inline int gar_sym_packed_doubles(int n) { return n * (n + 1) / 2;
 // unchanged.  The sweep reads 23.9 KB instead of 29.5 KB per knot at (36, 12).  The terminal knot stays full.
 // gar_hip_upload_stage / gar_hip_upload_packed / gar_hip_update_lq_subproblem_device pack, gar_hip_download_packed
 // and gar_hip_get_kkt unpack; gar_hip_device_sizes reports the format to device-resident producers.
-// (-DGAR_QR_PACKED=0: full blocks everywhere, the A/B of scripts/ab_vxx_packed.py)
-#ifndef GAR_QR_PACKED
-#define GAR_QR_PACKED 1
-#endif
 //   element (i, j), i >= j, of an n x n block
 GAR_HD static inline int gar_lower_index(int n, int i, int j) { return i + ((2 * n - j - 1) * j) / 2; }
 

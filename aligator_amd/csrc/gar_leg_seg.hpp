@@ -134,9 +134,7 @@ __host__ __device__ inline int leg_prepare_lds_doubles(int nx, int nu) { // V' |
   return a2(nx * nx) + 3 * a2(nx * nu) + 2 * a2(nu * nu) + a2(GAR_LDL_PANEL * nu) + 2 * a2(nu) + 64;
 }
 
-#ifndef GAR_LEG_PARAM_THREADS
 #define GAR_LEG_PARAM_THREADS 1024
-#endif
 // ---- (2) the parameter part, split by what is sequential ---------------------------------------------------------
 // Of the recursion above only  Vxt_t = Aff_t^T Vxt_{t+1}  chains the stages of a leg; everything else of stage t is a
 // function of Vxt_{t+1} (and of that stage's own operands), and Vtt / vt are running sums of per-stage increments:
@@ -269,9 +267,7 @@ __global__ void __launch_bounds__(GAR_LEG_PARAM_THREADS) gar_leg_param_chain(Leg
   }
 }
 
-#ifndef GAR_LEG_STAGE_THREADS
 #define GAR_LEG_STAGE_THREADS 512
-#endif
 // grid (N + 1, batch) x GAR_LEG_STAGE_THREADS
 __global__ void __launch_bounds__(GAR_LEG_STAGE_THREADS) gar_leg_param_stage(LegParamParams P) {
   const WG w = wg_self();

@@ -100,7 +100,7 @@ template <int NX, int NU, int NC = 0> struct MfmaCfg {
   // fallback solves in place there; sub (16) and piv+ctrl (16 doubles) follow
   static constexpr int oG2 = (oVp + NX + 1) & ~1;
   static constexpr int oBk = oG2 + NU * PG + 16;
-  // (gar_backward_mfma, GAR_MFMA_EARLY_FACTOR: L of Rhat, 1 / d_k and the verdict, handed from the worker wave that
+  // (gar_backward_mfma, EARLY_FACTOR: L of Rhat, 1 / d_k and the verdict, handed from the worker wave that
   // factorises to wave 3, which solves)
   static constexpr int oLf = oBk + 16 + 16;
   static constexpr int total = oLf + NU * NU + NU + 2;
@@ -327,30 +327,17 @@ __device__ __forceinline__ void wave_flush_vxx(const double *V, double *dst, int
     VO::write(dst, q, lane, vbuf[q]);
 }
 
-#ifndef GAR_MFMA_EARLY_FACTOR
-#define GAR_MFMA_EARLY_FACTOR 1
-#endif
-#ifndef GAR_MFMA_FLUSH16
-#define GAR_MFMA_FLUSH16 1
-#endif
-// (GAR_MFMA_EARLY_H measured and NOT adopted: backward 1.786 against 1.741 ms at batch 256 -- the tiles' latency was
-// hidden behind the first product already; profiles/r06_ab_mfma_4wave_early_hessian_tiles_not_kept.log)
-#ifndef GAR_MFMA_EARLY_H
-#define GAR_MFMA_EARLY_H 0
-#endif
 // (launch bounds: the kernel only ever runs with at most one workgroup per CU -- the library binds it while
 // batch <= #CUs --, so it could take the registers two resident workgroups share; measured: (256, 1) = 304 registers, no
 // scratch: 1.621 against 1.556 ms at batch 256, 1.494 against 1.528 at batch 1 -- kept at (256, 2) for the reporting point;
 // profiles/r06_ab_mfma_4wave_launch_bounds_not_kept.log)
-#ifndef GAR_MFMA_MIN_BLOCKS
 #define GAR_MFMA_MIN_BLOCKS 2
-#endif
 template <int NX, int NU>
 __global__ void __launch_bounds__(256, GAR_MFMA_MIN_BLOCKS) gar_backward_mfma(MfmaParams P) {
   using C = MfmaCfg<NX, NU>;
   static_assert(C::TW <= 3 && NU <= 16, "one column tile per worker wave (3 workers), NW <= 64");
   // Rhat (rows / columns NX .. NW-1) inside the LAST tile column alone: the worker that holds it factorises it
-  constexpr bool EARLY_FACTOR = (GAR_MFMA_EARLY_FACTOR != 0) && (NX >= 16 * (C::TW - 1));
+  constexpr bool EARLY_FACTOR = NX >= 16 * (C::TW - 1);
   constexpr int NW = C::NW, PK = C::PK, PG = C::PG;
   double *sm = gar_smem;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -374,9 +361,7 @@ __global__ void __launch_bounds__(256, GAR_MFMA_MIN_BLOCKS) gar_backward_mfma(Mf
       const int j = e / NX, i = e - j * NX; // column-major element (i, j)
       const double v = (i >= j) ? rec[C::tQ + e] : rec[C::tQ + i * NX + j];
       V[i * PK + j] = v; // symmetrised from lower, as the consumer stage does (:216)
-      if (!GAR_VXX_PACKED)
-        out[C::tVxx + e] = v;
-      else if (i >= j)
+      if (i >= j)
         out[C::tVxx + gar_sym_index(1, NX, i, j)] = v; // (packed lower triangle: gar_layout.h)
     }
     for (int e = tid; e < NX; e += 256) {
@@ -407,9 +392,7 @@ __global__ void __launch_bounds__(256, GAR_MFMA_MIN_BLOCKS) gar_backward_mfma(Mf
     const int c = 16 * tj + li;               // this lane's column in tile tj
     const int cc = c < NX ? c : NX - 1;
     double4_t Hc[C::TW]; // H tiles (ti, tj), ti >= tj
-    // C-init of H from the knot record (lower elements).  GAR_MFMA_EARLY_H: the tiles of knot t - 1 are requested at the
-    // END of stage t, before its last workgroup barrier -- a fence the compiler does not move loads across -- instead
-    // of at the start of stage t - 1, where their HBM latency had only the first product to hide behind
+    // C-init of H from the knot record (lower elements)
     auto load_h = [&](int t) {
       const double *rec = prob + P.in_off0 + P.slot(t) * P.in_rec;
       if (tj < C::TW) {
@@ -422,14 +405,11 @@ __global__ void __launch_bounds__(256, GAR_MFMA_MIN_BLOCKS) gar_backward_mfma(Mf
           }
       }
     };
-    if (GAR_MFMA_EARLY_H && N > 0)
-      load_h(N - 1);
     for (int t = N - 1; t >= 0; --t) {
       GAR_MARK(0)
       double *out = fac + P.slot(t) * P.fac_rec;
       const double *Ft = sm + ((t & 1) ? C::oFt1 : C::oFt0);
-      if (!GAR_MFMA_EARLY_H)
-        load_h(t);
+      load_h(t);
       if (tj < C::TW) {
         // S1: P(:, tj) = V' F(:, tj)            (:216-221, AtV / BtV fused)
         double4_t Pt[C::TX];
@@ -559,28 +539,16 @@ __global__ void __launch_bounds__(256, GAR_MFMA_MIN_BLOCKS) gar_backward_mfma(Mf
           }
       }
       GAR_MARK(7)
-      if (GAR_MFMA_EARLY_H && t > 0)
-        load_h(t - 1);
       __syncthreads(); // C: V, vn, Ft[next] complete
       GAR_MARK(8)
-#if GAR_MFMA_FLUSH16
       { // Vxx -> HBM (packed lower triangle: gar_layout.h) in 16-byte pieces, the chunks dealt over the three workers:
         // two stores per lane instead of seven 8-byte ones behind an index division (round 6)
-        using VO = VxxOut<NX, GAR_VXX_PACKED != 0, PK>;
+        using VO = VxxOut<NX, true, PK>;
 #pragma unroll
         for (int q0 = 0; q0 < VO::NCH; q0 += 3)
           if (q0 + wave < VO::NCH)
             VO::write(out + C::fVxx, q0 + wave, lane, VO::read(V, q0 + wave, lane));
       }
-#else
-      for (int e = tid; e < NX * NX; e += 192) { // Vxx -> HBM (packed lower triangle: gar_layout.h)
-        const int j = e / NX, i = e - j * NX;
-        if (!GAR_VXX_PACKED)
-          out[C::fVxx + e] = V[i * PK + j];
-        else if (i >= j)
-          out[C::fVxx + gar_sym_index(1, NX, i, j)] = V[i * PK + j];
-      }
-#endif
       GAR_MARK(9)
     }
   } else {
@@ -781,9 +749,8 @@ template <int NX, int NC = 0> struct FwdStage {
   double2_t gz[NC > 0 ? NX / 2 : 1];
   // Vxx' of the next stage.  Packed records (gar_layout.h): this lane's 16-byte pieces of the packed lower triangle,
   // fetched linearly (whole lines, 6 requests per lane at nx = 36) -- they go through LDS to become rows in
-  // fwd_step.  Full records (-DGAR_VXX_PACKED=0): row iv itself, gathered from the lower triangle.
-  double2_t vp[GAR_VXX_PACKED ? VxxOut<NX, true>::NCH : 1];
-  double vrow[GAR_VXX_PACKED ? 1 : NX];
+  // fwd_step.
+  double2_t vp[VxxOut<NX, true>::NCH];
   double ff, vxn, ffz;
 };
 
@@ -808,17 +775,13 @@ __device__ __forceinline__ void fwd_load(const MfmaFwdParams &P, const double *f
       S.gz[m] = *reinterpret_cast<const double2_t *>(rec + C::fFB + m * 2 * NW + 2 * rz);
     S.ffz = rec[C::fFF + rz];
   }
-  if (GAR_VXX_PACKED) {
+  {
     using VO = VxxOut<NX, true>;
 #pragma unroll
     for (int q = 0; q < VO::NCH; ++q) {
       const int e = 64 * q + lane, ec = (64 * q + 63 < VO::NP2 || e < VO::NP2) ? e : VO::NP2 - 1;
-      S.vp[GAR_VXX_PACKED ? q : 0] = *reinterpret_cast<const double2_t *>(recn + oVn + 2 * ec);
+      S.vp[q] = *reinterpret_cast<const double2_t *>(recn + oVn + 2 * ec);
     }
-  } else { // full block: lower triangle only (column j, row iv for j <= iv; this lane's own column below)
-#pragma unroll
-    for (int j = 0; j < NX; ++j)
-      S.vrow[GAR_VXX_PACKED ? 0 : j] = recn[oVn + (iv >= j ? j * NX + iv : iv * NX + j)];
   }
   S.ff = rec[C::fFF + r];
   S.vxn = recn[ovn + iv];
@@ -829,14 +792,14 @@ __device__ __forceinline__ double fwd_step(const MfmaFwdParams &P, double *sol, 
                                            double xs, const FwdStage<NX, NC> &S, double *vb, int iv) {
   using C = MfmaCfg<NX, NU, NC>;
   constexpr int NW = C::NW;
-  if (GAR_VXX_PACKED) { // the packed triangle of Vxx' -> LDS (the rows are read back after the products below)
+  { // the packed triangle of Vxx' -> LDS (the rows are read back after the products below)
     using VO = VxxOut<NX, true>;
     wave_sync(); // (the previous stage's row reads are done)
 #pragma unroll
     for (int q = 0; q < VO::NCH; ++q) {
       const int e = 64 * q + lane;
       if (64 * q + 63 < VO::NP2 || e < VO::NP2)
-        *reinterpret_cast<double2_t *>(&vb[2 * e]) = S.vp[GAR_VXX_PACKED ? q : 0];
+        *reinterpret_cast<double2_t *>(&vb[2 * e]) = S.vp[q];
     }
     wave_sync();
   }
@@ -864,7 +827,7 @@ __device__ __forceinline__ double fwd_step(const MfmaFwdParams &P, double *sol, 
   }
   // lbd' = vx' + Vxx' x'  (:369-371); x'_j sits in lane NU + j
   double lam = S.vxn, lam1 = 0.0;
-  if (GAR_VXX_PACKED) {
+  {
     // row iv of the symmetric matrix from its packed lower triangle (gar_sym_index): elements (iv, j), j <= iv, at
     // cj + iv (consecutive lanes, consecutive addresses); (j, iv), j > iv, at lowbase + j
     const int lowbase = 2 * iv < NX ? iv * NX : (NX - 1 - iv) * (NX + 1) + 1;
@@ -878,12 +841,6 @@ __device__ __forceinline__ double fwd_step(const MfmaFwdParams &P, double *sol, 
     for (int j = 0; j < NX; j += 2) {
       lam = __builtin_fma(vr[j], lane_bcast(acc, NU + j), lam);
       lam1 = __builtin_fma(vr[j + 1], lane_bcast(acc, NU + j + 1), lam1);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < NX; j += 2) {
-      lam = __builtin_fma(S.vrow[GAR_VXX_PACKED ? 0 : j], lane_bcast(acc, NU + j), lam);
-      lam1 = __builtin_fma(S.vrow[GAR_VXX_PACKED ? 0 : j + 1], lane_bcast(acc, NU + j + 1), lam1);
     }
   }
   lam += lam1;

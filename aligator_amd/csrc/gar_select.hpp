@@ -7,7 +7,7 @@
 template <int NX, int NU> void bind_mfma(gar_hip_solver *s) {
   s->mfma_kernel = gar::gar_backward_mfma<NX, NU>;
   s->mfma_fwd_kernel = gar::gar_forward_mfma<NX, NU>;
-  s->mfma_fwd_lds_bytes = GAR_VXX_PACKED ? sizeof(double) * (size_t)gar_sym_packed_doubles(NX) : 0;
+  s->mfma_fwd_lds_bytes = sizeof(double) * (size_t)gar_sym_packed_doubles(NX);
   s->fb_t2 = true;
   s->mfma_lds_doubles = gar::MfmaCfg<NX, NU>::total;
   s->kernel_name = "mfma<" + std::to_string(NX) + "," + std::to_string(NU) + ">";
@@ -37,19 +37,16 @@ template <int NX, int NU> void bind_mfma(gar_hip_solver *s) {
     // quarter of the CU's LDS (four waves per CU)
     const int with_init = gar::WaveCfg<NX, NU>::total_with_init(s->nc0);
     s->wave_fused_init = (size_t)with_init * sizeof(double) <= 40 * 1024 && s->nth0 == 0;
-    // (F-DMA: the next knot's [A | B] image lies behind `total`, under the fused initial stage's kkt0)
-    const int sweep = GAR_F_DMA ? gar::WaveCfg<NX, NU>::total_fdma : gar::WaveCfg<NX, NU>::total;
+    const int sweep = gar::WaveCfg<NX, NU>::total;
     s->wave_lds_doubles = s->wave_fused_init ? std::max(with_init, sweep) : sweep;
     s->waves_per_block = 1; // one 64-thread workgroup per problem (constant LDS base)
     s->kernel_name = "wave<" + std::to_string(NX) + "," + std::to_string(NU) + ">";
-    s->qr_packed = GAR_QR_PACKED != 0; // the sweep reads only the lower triangles of Q and R (gar_layout.h)
+    s->qr_packed = true; // the sweep reads only the lower triangles of Q and R (gar_layout.h)
     // the pipelined sweep's roll-out (gar_hip_set_pipeline): reads the packed Vxx records
-    if (GAR_VXX_PACKED) {
-      s->lean_fwd_kernel = gar::gar_forward_lean<NX, NU>;
-      s->wave_half_kernel = gar::gar_backward_wave_half<NX, NU>;
-      s->lean_fwd_used = gar::LeanFwdCfg<NX, NU>::USED; // (what it uses; pipe_plan decides what it asks for)
-      s->wave_lds_doubles_small = sweep;
-    }
+    s->lean_fwd_kernel = gar::gar_forward_lean<NX, NU>;
+    s->wave_half_kernel = gar::gar_backward_wave_half<NX, NU>;
+    s->lean_fwd_used = gar::LeanFwdCfg<NX, NU>::USED; // (what it uses; pipe_plan decides what it asks for)
+    s->wave_lds_doubles_small = sweep;
   }
 }
 
@@ -67,10 +64,10 @@ template <int NX, int NU> void bind_wide(gar_hip_solver *s) {
   s->waves_per_block = 1;
   s->fb_t2 = false;
   if (pair) {
-    // packed records (gar_wave_pair.hpp, GAR_PAIR_PACKED): lower triangles of Q, R in the knots, of Vxx in the factors
+    // packed records (gar_wave_pair.hpp): lower triangles of Q, R in the knots, of Vxx in the factors
     // -- with the roll-out that reads them (the any-dimension roll-out reads the flag from its parameters)
     // (the any-dimension roll-out reads full Vxx blocks: GAR_HIP_WIDE=generic-forward keeps the full records)
-    constexpr bool PKD = GAR_PAIR_PACKED && GAR_QR_PACKED && GAR_VXX_PACKED && (NX % 4 == 0);
+    constexpr bool PKD = NX % 4 == 0;
     if (PKD && !generic_fwd) {
       s->wave_kernel = gar::gar_backward_pair<NX, NU, PKD>;
       s->qr_packed = true;
@@ -178,14 +175,14 @@ template <int NX, int NU, int NC> void bind_cstr(gar_hip_solver *s) {
   s->wave_coupled_kernel = gar::gar_backward_wave_coupled<NX, NU, NC>;
   s->wave_bk_kernel = gar::gar_backward_wave_bk<NX, NU, NC>;
   s->mfma_fwd_kernel = gar::gar_forward_mfma<NX, NU, NC>;
-  s->mfma_fwd_lds_bytes = GAR_VXX_PACKED ? sizeof(double) * (size_t)gar_sym_packed_doubles(NX) : 0;
+  s->mfma_fwd_lds_bytes = sizeof(double) * (size_t)gar_sym_packed_doubles(NX);
   s->fb_t2 = true;
   const int with_init = gar::WaveCfg<NX, NU, NC>::total_with_init(s->nc0);
   s->wave_fused_init = (size_t)with_init * sizeof(double) <= 64 * 1024 && s->nth0 == 0;
   s->wave_lds_doubles = s->wave_fused_init ? with_init : gar::WaveCfg<NX, NU, NC>::total;
   s->waves_per_block = 1;
   s->kernel_name = "wave<" + std::to_string(NX) + "," + std::to_string(NU) + "," + std::to_string(NC) + ">";
-  s->qr_packed = GAR_QR_PACKED != 0; // the chain's three kernels read only the lower triangles of Q and R (gar_layout.h)
+  s->qr_packed = true; // the chain's three kernels read only the lower triangles of Q and R (gar_layout.h)
 }
 
 void select_kernel(gar_hip_solver *s) {
@@ -262,7 +259,7 @@ void select_kernel(gar_hip_solver *s) {
     if (nx == 36 && nu == 12 && nc == 32) bind_cstr<36, 12, 32>(s);
     else if (nx == 16 && nu == 8 && nc == 8) bind_cstr<16, 8, 8>(s);
     else if (nx == 8 && nu == 4 && nc == 4) bind_cstr<8, 4, 4>(s);
-    s->vxx_packed = GAR_VXX_PACKED && s->fb_t2; // (serial one-wave family: gar_layout.h)
+    s->vxx_packed = s->fb_t2; // (serial one-wave family: gar_layout.h)
     return;
   }
   if (nx == 36 && nu == 12) bind_mfma<36, 12>(s);
@@ -273,7 +270,7 @@ void select_kernel(gar_hip_solver *s) {
   else if (nx == 8 && nu == 4) bind_mfma<8, 4>(s);
   else if (nx == 56 && nu == 24) bind_wide<56, 24>(s);
   // the serial one-wave family keeps the lower triangle of Vxx, packed (gar_layout.h); round 6: the two-wave wide family too
-  s->vxx_packed = GAR_VXX_PACKED && (s->fb_t2 || s->wide_vxx_packed);
+  s->vxx_packed = s->fb_t2 || s->wide_vxx_packed;
 }
 
 // (nx, nu) shapes with kernels of their own (bind_mfma / bind_leg / bind_wide / bind_seg_leg above)
@@ -421,7 +418,7 @@ int configure_padded_or_not(gar_hip_solver *s) {
     s->cseg_on = false;
     const char *cs = gar_option("GAR_HIP_CSTR_SEG_LEGS");
     const int nx = s->dims5[0], nu = s->dims5[1], nc = s->dims5[2];
-    bool uniform_nc = nc > 0 && GAR_QR_PACKED != 0 && GAR_VXX_PACKED != 0;
+    bool uniform_nc = nc > 0;
     for (int t = 0; t <= s->horizon; ++t)
       uniform_nc &= s->dims5[5 * (size_t)t + 2] == nc;
     if (uniform_nc && !(cs && cs[0] == '0') && gar::cseg_bind(nx, nu, nc, &s->cseg) &&

@@ -41,22 +41,6 @@
 
 namespace gar {
 
-// F-DMA (see WaveCfg::oF): measured and NOT adopted -- same box, alternating launches, batch 4 096: backward 11.32 ms
-// with it against 10.58 ms without (profiles/r05_ab_f_operands_by_lds_dma_not_kept.log), results bit for bit the same.
-// The 27 operand loads of sixteen 32-byte pieces each are not what the stage waits for.  `make fdma` builds it.
-#ifndef GAR_F_DMA
-#define GAR_F_DMA 0
-#endif
-#ifndef GAR_COUPLED_REFRESH_LANE
-#define GAR_COUPLED_REFRESH_LANE 1
-#endif
-#ifndef GAR_SWEEP_REFRESH_LANE  // ... and for the unconstrained headline sweep
-#define GAR_SWEEP_REFRESH_LANE 0
-#endif
-#ifndef GAR_CSTR_REFRESH_LANE   // the same for the decoupled constrained stage (first kernel of the chain): by itself
-#define GAR_CSTR_REFRESH_LANE 1 // +5.5 % slower; together with GAR_CSTR_EARLY_C (gar_wave2.hpp), which needs the room, -9 %
-#endif
-
 template <int NX, int NU, int NC = 0> struct WaveCfg {
   using M = MfmaCfg<NX, NU, NC>;
   static constexpr int NW = NX + NU, TX = M::TX, TW = M::TW, KS = M::KS, KU = M::KU;
@@ -68,22 +52,10 @@ template <int NX, int NU, int NC = 0> struct WaveCfg {
   // 16k+4b+j and D_b[i][j] in lane 16i+4b+j (measured, scripts/ubench/mfma4x4_probe.cpp) the B
   // operand and the result have exactly the 16x16x4 B-operand layout (column on lane&15, k or
   // row on lane>>4), so they drop into the same registers.
-#ifdef GAR_NO_REM4
-  static constexpr bool REM4 = false;
-#else
   static constexpr bool REM4 = (NX % 16 == 4) && (KST == 1);
-#endif
   // Pitch of V in LDS: NX (unpadded).  Its MFMA operand reads V[(16 t + li) * PK + 4 s + lk] are 2-way bank conflicts
-  // (lanes li and li + 8); a pitch of NX + 2 makes them conflict-free ((PK li + lk) mod 32 is then a bijection) and
-  // is supported (-DGAR_V_PITCH_PAD=1: every flush is a gather with the pitch) -- measured: SQ_LDS_BANK_CONFLICT
-  // falls from 8.1 % to 4.3 % of the wave cycles (45 % -> 30 % of the LDS-active cycles) and SQ_WAVE_CYCLES does not
-  // move (-0.3 %; profiles/r03_sq_lds_pitch.log); A/B on one box, alternating launches: backward 11.25 ms padded
-  // against 11.07 ms unpadded (scripts/ab_vxx_packed.py).  The conflicts hide behind the 64-cycle MFMAs they feed.
-  // Not used.
-#ifndef GAR_V_PITCH_PAD
-#define GAR_V_PITCH_PAD 0
-#endif
-  static constexpr int PK = (GAR_V_PITCH_PAD && NX % 4 == 0) ? NX + 2 : NX, PG = M::PG;
+  // (lanes li and li + 8); they hide behind the 64-cycle MFMAs they feed.
+  static constexpr int PK = NX, PG = M::PG;
   // tile row / register of H holding Shat^T row u = 4s' + lk (rows NX + u)
   __host__ __device__ static constexpr int shTile(int s) { return (NX + 4 * s) >> 4; }
   __host__ __device__ static constexpr int shReg(int s) { return ((NX + 4 * s) & 15) >> 2; }
@@ -103,13 +75,6 @@ template <int NX, int NU, int NC = 0> struct WaveCfg {
   static constexpr int oDump = (oBk + 2 * BKS + 1) & ~1; // 2 doubles: target of masked-out LDS writes
   static constexpr int oFlag = oDump + 2;           // MODE 3: verdict of the factorisation (as a double)
   static constexpr int total = oDump + 4;
-  // F-DMA (GAR_F_DMA, the serial one-wave sweep NC = 0): [A | B] of the NEXT knot, requested into LDS at the start
-  // of the stage by global_load_lds (14 linear 1 KiB pieces at (36, 12) instead of 27 loads of sixteen 32-byte
-  // pieces each, no registers), read as MFMA operands where the stage used to load them from HBM.  It lies behind
-  // everything the stage uses -- where the fused initial stage's kkt0 goes once the sweep is over.
-  static constexpr int oF = (total + 1) & ~1;
-  static constexpr int f_doubles = NX * NW;
-  static constexpr int total_fdma = oF + f_doubles;
   // fused initial stage (after the sweep): the packed lower triangle of kkt0 = [Vxx0 G0^T; G0 0]
   // and its right-hand side overlay everything but V
   static constexpr int oK0 = oG;
@@ -1218,7 +1183,7 @@ __device__ __forceinline__ void wave_stage(const MfmaParams &P, double *sm, cons
   wave_sync();
   // ---- knot t-1: its Hessian tiles replace H  (NC > 0 is the serial constrained chain, whose records keep Q and R
   // as packed lower triangles like the plain sweep's: gar_layout.h; the leg kernels run this stage with NC = 0)
-  wave_load_b<NX, NU, WaveLane<NX, NU, NC>, (GAR_QR_PACKED && NC > 0 && !MfmaCfg<NX, NU, NC>::WIDE)>(recn, L, S);
+  wave_load_b<NX, NU, WaveLane<NX, NU, NC>, (NC > 0 && !MfmaCfg<NX, NU, NC>::WIDE)>(recn, L, S);
   GAR_WMARK(9)
   // ---- Vxx -> HBM, 16 B per lane: column-major and symmetric, or (PACKV: the serial family, gar_layout.h) the
   // packed lower triangle
@@ -1277,7 +1242,7 @@ __device__ __forceinline__ void gar_backward_wave_body(const MfmaParams &P, int 
       return;
   }
   // Q, R of the knots as packed lower triangles (gar_layout.h): the one-wave serial sweeps
-  constexpr bool QP = GAR_QR_PACKED && !M::WIDE; // (the constrained chain NC > 0 too)
+  constexpr bool QP = !M::WIDE; // (the constrained chain NC > 0 too)
   WaveLane<NX, NU, NC> L;
   wave_lane_init<NX, NU, NC, QP>(L, lane);
   WaveStage<NX, NU> S;
@@ -1294,7 +1259,7 @@ __device__ __forceinline__ void gar_backward_wave_body(const MfmaParams &P, int 
     const double *rn = fac + P.slot(tstart + 1) * P.fac_rec;
     for (int e = lane; e < NX * NX; e += 64) {
       const int j = e / NX, i = e - j * NX;
-      V[i * PK + j] = rn[M::fVxx + gar_sym_index(GAR_VXX_PACKED && !M::WIDE, NX, i, j)]; // (packed lower triangle: gar_layout.h)
+      V[i * PK + j] = rn[M::fVxx + gar_sym_index(!M::WIDE, NX, i, j)]; // (packed lower triangle: gar_layout.h)
     }
     if (lane < NX)
       vn[lane] = rn[M::fvx + lane];
@@ -1307,7 +1272,7 @@ __device__ __forceinline__ void gar_backward_wave_body(const MfmaParams &P, int 
       for (int k = 0; k < NC; ++k) // (C^T Z)(i, j), Z = C / mu
         v = __builtin_fma(rec[M::tC + i * NC + k], rec[M::tC + j * NC + k] / P.mueq, v);
       V[i * PK + j] = v; // symmetrised from lower, as the consumer stage does (:216)
-      if (M::WIDE || !GAR_VXX_PACKED)
+      if (M::WIDE)
         out[M::tVxx + e] = v;
       else if (i >= j)
         out[M::tVxx + gar_sym_index(1, NX, i, j)] = v; // (packed lower triangle: gar_layout.h)
@@ -1336,23 +1301,15 @@ __device__ __forceinline__ void gar_backward_wave_body(const MfmaParams &P, int 
                                                                    : fac + P.fac_offN + M::tVxx;
   for (int t = tstart; t >= 0; --t) {
     if constexpr (NC == 0) {
-#if GAR_SWEEP_REFRESH_LANE
-      const int lane_t = lane + fence0(S.fi);
-      WaveLane<NX, NU, NC> Lt;
-      wave_lane_init<NX, NU, NC, QP>(Lt, lane_t);
-      wave_stage2<NX, NU, 0, false, (GAR_F_DMA != 0) && !M::WIDE>(P, sm, prob, fac, t, lane_t, Lt, S, failed, vflush, tracing);
-#else
-      wave_stage2<NX, NU, 0, false, (GAR_F_DMA != 0) && !M::WIDE>(P, sm, prob, fac, t, lane, L, S, failed, vflush, tracing);
-#endif
+      wave_stage2<NX, NU, 0, false>(P, sm, prob, fac, t, lane, L, S, failed, vflush, tracing);
     } else {
       if constexpr (PHASE == 2) {
         if (lane == 0)
           atomicAdd(&P.slow[3], 1);
-        wave_stage<NX, NU, 0, 0, NC, GAR_VXX_PACKED != 0>(P, sm, prob, fac, t, lane, L, S, failed, tracing);
+        wave_stage<NX, NU, 0, 0, NC, true>(P, sm, prob, fac, t, lane, L, S, failed, tracing);
       } else {
         if (PHASE == 1 && lane == 0)
           atomicAdd(&P.slow[2], 1);
-#if GAR_COUPLED_REFRESH_LANE
         // The coupled stage held every one of the 512 registers AND 768 bytes of scratch per lane: the ~100 loop-invariant
         // lane offsets of WaveLane (and everything else the compiler derives from the lane index once, outside the stage
         // loop) lived in scratch and came back through vmcnt(0) waits inside the stage -- 1.42 x the algorithmic bytes
@@ -1360,15 +1317,12 @@ __device__ __forceinline__ void gar_backward_wave_body(const MfmaParams &P, int 
         // lane index the compiler cannot prove loop-invariant costs ~100 integer instructions per stage and leaves the
         // kernel at 432 registers, no scratch: backward 12.63 -> 7.98 ms at batch 1 024, N = 256 (0.198 -> 0.314 of the
         // HBM roofline), results BITWISE the same (profiles/r06_ab_coupled_lane_offsets_rederived_per_stage.log).
-        constexpr bool REFRESH = PHASE == 1 || (GAR_CSTR_REFRESH_LANE != 0);
-        const int lane_t = REFRESH ? lane + fence0(S.fi) : lane;
+        // The decoupled stage (first kernel of the chain) does the same: by itself +5.5 % slower; together with the C
+        // operands fetched at the start of the stage (gar_wave2.hpp), which need the room, -9 %.
+        const int lane_t = lane + fence0(S.fi);
         WaveLane<NX, NU, NC> Lt;
-        if constexpr (REFRESH)
-          wave_lane_init<NX, NU, NC, QP>(Lt, lane_t);
-        if (!wave_stage2<NX, NU, NC, PHASE == 1>(P, sm, prob, fac, t, lane_t, REFRESH ? Lt : L, S, failed, vflush, tracing)) {
-#else
-        if (!wave_stage2<NX, NU, NC, PHASE == 1>(P, sm, prob, fac, t, lane, L, S, failed, vflush, tracing)) {
-#endif
+        wave_lane_init<NX, NU, NC, QP>(Lt, lane_t);
+        if (!wave_stage2<NX, NU, NC, PHASE == 1>(P, sm, prob, fac, t, lane_t, Lt, S, failed, vflush, tracing)) {
           if (lane == 0) { // over to the next kernel of the chain from this knot on
             P.resume[b] = t;
             if (PHASE == 1)
@@ -1387,7 +1341,7 @@ __device__ __forceinline__ void gar_backward_wave_body(const MfmaParams &P, int 
   }
   if constexpr (PHASE < 2) {
     if (N > 0)
-      wave_flush_vxx<NX, GAR_VXX_PACKED && !M::WIDE, PK>(V, vflush, lane);
+      wave_flush_vxx<NX, !M::WIDE, PK>(V, vflush, lane);
   }
   // ---- initial stage (proximal-riccati.hxx:42-60), fused: kkt0 = [Vxx0 G0^T; G0 0] is
   // Bunch-Kaufman-factorised by this wave right away (packed lower triangle in LDS, read from

@@ -30,6 +30,29 @@
 #pragma once
 #include "gar_wave.hpp"
 
+// ---- compile-time switches of this file (besides -DGAR_TRACE, the cycle stamps of the `make trace` build).  Both are
+// off in the library; tests/test_ldl_blocked.py builds the emulator with each of them on and checks the coupled stage
+// against the oracle.
+// GAR_COUPLED_BLOCKED_LDL: the coupled stage's factorisation on the blocked wave-scope L D L^T (gar_ldl_blocked.hpp).
+// MEASURED AND NOT ADOPTED for the coupled stage (same box, alternating launches, 1 024 distinct problems):
+//   * first form (profiles/r06_ab_coupled_blocked_ldl_not_kept.log, r06_trace_cstr_coupled.log): backward 15.59 ms
+//     against 12.71 with the register version -- every LDS address of the routine is a function of the lane alone, the
+//     compiler hoisted them out of the stage loop into a kernel that was full and reloaded them from SCRATCH inside
+//     the factorisation (95 reloads, each behind a vmcnt(0)); 84.6 k cycles for the phase;
+//   * with the lane index made opaque per stage (fence0: the addresses are computed where they are used):
+//     11.98 ms against 12.70 (r06_ab_coupled_blocked_ldl_without_address_spills.log);
+//   * and once the SAME cure was applied to the whole coupled stage (lane offsets re-derived per stage, gar_wave.hpp: no scratch
+//     at all, 432 registers) the register version is the faster one: 7.98 ms against 8.54 blocked
+//     (r06_ab_coupled_lane_offsets_rederived_per_stage.log).  Results equal to 2e-15 throughout.
+#ifndef GAR_COUPLED_BLOCKED_LDL
+#define GAR_COUPLED_BLOCKED_LDL 0
+#endif
+// GAR_COUPLED_HYBRID_LDL -- Rhat's columns as one DPP panel with the Schur complement on MFMA tiles, the rest in registers --
+// measured and NOT adopted: 7.95 ms against 7.52, profiles/r06_ab_coupled_hybrid_ldl_not_kept.log
+#ifndef GAR_COUPLED_HYBRID_LDL
+#define GAR_COUPLED_HYBRID_LDL 0
+#endif
+
 namespace gar {
 
 // LDS hand-off between lanes of ONE wave.  The LDS executes a wave's instructions in order, so a
@@ -277,38 +300,11 @@ __device__ __forceinline__ unsigned long long wave_ballot(bool p) {
 } // namespace gar
 // (the blocked wave-scope L D L^T: built on row_bcast / wave_ballot / wave_lds_order above, used by the coupled stage below)
 #include "gar_ldl_blocked.hpp"
-// MEASURED AND NOT ADOPTED for the coupled stage (same box, alternating launches, 1 024 distinct problems):
-//   * first form (profiles/r06_ab_coupled_blocked_ldl_not_kept.log, r06_trace_cstr_coupled.log): backward 15.59 ms
-//     against 12.71 with the register version -- every LDS address of the routine is a function of the lane alone, the
-//     compiler hoisted them out of the stage loop into a kernel that was full and reloaded them from SCRATCH inside
-//     the factorisation (95 reloads, each behind a vmcnt(0)); 84.6 k cycles for the phase;
-//   * with the lane index made opaque per stage (fence0: the addresses are computed where they are used):
-//     11.98 ms against 12.70 (r06_ab_coupled_blocked_ldl_without_address_spills.log);
-//   * and once the SAME cure was applied to the whole coupled stage (GAR_COUPLED_REFRESH_LANE, gar_wave.hpp: no scratch
-//     at all, 432 registers) the register version is the faster one: 7.98 ms against 8.54 blocked
-//     (r06_ab_coupled_lane_offsets_rederived_per_stage.log).  Results equal to 2e-15 throughout.
-#ifndef GAR_COUPLED_BLOCKED_LDL
-#define GAR_COUPLED_BLOCKED_LDL 0
-#endif
-#ifndef GAR_COUPLED_RELOAD_C   // 1: the C operands are loaded again behind the KKT solve (as until round 6); 0: they
-#define GAR_COUPLED_RELOAD_C 0 //    stay in registers (the kernel has room since GAR_COUPLED_REFRESH_LANE): 7.82 -> 7.54 ms
-#endif
-// (the hybrid -- Rhat's columns as one DPP panel with the Schur complement on MFMA tiles, the rest in registers --
-// measured and NOT adopted: 7.95 ms against 7.52, profiles/r06_ab_coupled_hybrid_ldl_not_kept.log)
-// GAR_CSTR_EARLY_C (round 6; with GAR_CSTR_REFRESH_LANE, gar_wave.hpp): the decoupled constrained stage requests its
+// The decoupled constrained stage (round 6; with its lane offsets re-derived per stage, gar_wave.hpp) requests its
 // constraint operands C, d at the START of the stage instead of behind the factorisation (where the leave-early branch
 // keeps the compiler from moving them up): backward 4.54 -> 4.13 ms at batch 1 024 (0.551 -> 0.606 of the roofline),
 // bitwise.  It needs the 80 registers the re-derived lane offsets free: without them the operands spill (5.99 ms).
 // profiles/r06_ab_constrained_stage_c_operands_requested_early.log
-#ifndef GAR_CSTR_EARLY_C
-#define GAR_CSTR_EARLY_C 1
-#endif
-#ifndef GAR_CSTR_SLOT_C
-#define GAR_CSTR_SLOT_C 1
-#endif
-#ifndef GAR_COUPLED_HYBRID_LDL
-#define GAR_COUPLED_HYBRID_LDL 0
-#endif
 namespace gar {
 // The register LDL^T of wave_ldl_fast_neg on rows already in registers (a[j] = Rhat(row, j)), under
 // the COMPLETE pivot rule: a column that fails the first test is checked out of line against the
@@ -379,9 +375,6 @@ __device__ __forceinline__ int wave_ldl_fast_neg_pre(int lane, double (&a)[NU], 
 // factorisation, B for Aff, the gains' stores, the next knot's loads, the V tiles -> LDS -- behind
 // the MFMAs of the tile columns, of Aff and of Vxx.
 #define GAR_SB __builtin_amdgcn_sched_barrier(0)
-#ifndef GAR_F_DMA_YOUNGER
-#define GAR_F_DMA_YOUNGER 24
-#endif
 
 // NC > 0 (equality constraints C x + D u + d = 0 on the knot, riccati-kernel.hxx:232-262): this stage
 // serves the DECOUPLED case D = 0 -- what the reference's own generator and benchmark produce
@@ -398,7 +391,7 @@ __device__ __forceinline__ int wave_ldl_fast_neg_pre(int lane, double (&a)[NU], 
 // (ldl_solve_mfma4_packed).  Returns 0 only when Bunch-Kaufman interchanges or takes a 2x2 pivot
 // somewhere: the caller then runs the stage with the LDS Bunch-Kaufman (wave_stage).
 // NC = 0: always returns 1.
-template <int NX, int NU, int NC = 0, bool COUPLED = false, bool FDMA = false>
+template <int NX, int NU, int NC = 0, bool COUPLED = false>
 __device__ __forceinline__ int wave_stage2(const MfmaParams &P, double *sm, const double *prob,
                                            double *fac, int t, int lane,
                                            const WaveLane<NX, NU, NC> &L, WaveStage<NX, NU> &S,
@@ -434,15 +427,6 @@ __device__ __forceinline__ int wave_stage2(const MfmaParams &P, double *sm, cons
 #define GAR_WMARK(id)
 #endif
   GAR_WMARK(0)
-  static_assert(!FDMA || (NC == 0 && !WIDE && !COUPLED), "F-DMA: the plain serial stage");
-  // F-DMA: [A | B] of knot t-1 on its way into LDS now (the buffer's previous content -- this knot's -- went into
-  // the F operand registers during the previous stage); read back in the Aff phase below, a stage's worth of
-  // MFMAs later.  Fb: the buffer addressed like the knot record (the lane offsets of F include kA).
-  [[maybe_unused]] const double *Fb = sm + C::oF - M::kA;
-  if constexpr (FDMA) {
-    if (t > 0)
-      wave_dma<8 * C::f_doubles>(recn + M::kA, reinterpret_cast<char *>(sm + C::oF), lane);
-  }
   // ---- operands of the vector recursion: vx'[4s+lk] (LDS), f[4s+lk] (this knot: L2 hit) ------
   double vxs[KS], fs[KS];
 #pragma unroll
@@ -482,10 +466,10 @@ __device__ __forceinline__ int wave_stage2(const MfmaParams &P, double *sm, cons
     for (int sc = 0; sc < KC; ++sc)
       dz[sc] = ldg_b(rec, M::kd + 4 * sc, 8u * (unsigned)lk);
   };
-  // (GAR_CSTR_EARLY_C: the constraint operands are requested at the START of the stage, like D -- they used to be
+  // (EARLY_C: the constraint operands are requested at the START of the stage, like D -- they used to be
   // requested behind the factorisation, where the stage's leave-early branch sits in front of them)
-  constexpr bool EARLY_C = NC > 0 && !COUPLED && (GAR_CSTR_EARLY_C != 0); // (the coupled stage has no room for them across its 44-row factorisation)
-  if constexpr (EARLY_C && !((GAR_CSTR_SLOT_C != 0) && !M::WIDE))
+  constexpr bool EARLY_C = NC > 0 && !COUPLED; // (the coupled stage has no room for them across its 44-row factorisation)
+  if constexpr (EARLY_C && M::WIDE)
     load_cop();
   double qri1 = 0.0; // WIDE: [q; r][64 + lane]
   if (WIDE)
@@ -496,10 +480,7 @@ __device__ __forceinline__ int wave_stage2(const MfmaParams &P, double *sm, cons
   constexpr int cR = NX >> 4; // first tile column holding control columns: Rhat needs tj >= cR
   // V' as the A operand of P = V'F: the same registers serve every tile column (the wide shapes
   // have no registers to spare for that: they read the operands from LDS at every use)
-#ifndef GAR_PRELOAD_V
-#define GAR_PRELOAD_V 1
-#endif
-  constexpr bool PRELOAD_V = !WIDE && GAR_PRELOAD_V;
+  constexpr bool PRELOAD_V = !WIDE;
   double Vop[PRELOAD_V ? (TXF > 0 ? TXF : 1) : 1][PRELOAD_V ? KS : 1], Vop4[PRELOAD_V ? KS : 1];
   if (PRELOAD_V) {
 #pragma unroll
@@ -517,12 +498,12 @@ __device__ __forceinline__ int wave_stage2(const MfmaParams &P, double *sm, cons
   double Bop[TX][KU]; // B of this knot as the A operand of Aff = A + B K: B[16ti+li][4s'+lk]
   double Bop4[KU];    // REM4: B[NX-4+i4][4s'+k4], the A operand of the 4x4x4 blocks
   // ---- memory work slotted behind the MFMAs of the tile columns tj < cR (list A) ----------------
-  using VO = VxxOut<NX, GAR_VXX_PACKED && !WIDE, PK>;
+  using VO = VxxOut<NX, !WIDE, PK>;
   constexpr int NCH = VO::NCH;
   constexpr int nA_flush = NCH + 2, nA_rows = NU, nA_bop = TX * KU + (C::REM4 ? KU : 0);
-  // (EARLY_C && GAR_CSTR_SLOT_C: the constraint operands C, d join the list instead of being issued in one burst at the
+  // (SLOT_C: the constraint operands C, d join the list instead of being issued in one burst at the
   // start of the stage -- 40 more loads behind the MFMAs of the state tile columns)
-  constexpr bool SLOT_C = EARLY_C && (GAR_CSTR_SLOT_C != 0) && !WIDE;
+  constexpr bool SLOT_C = EARLY_C && !WIDE;
   constexpr int nA_cop = SLOT_C ? TX * KC + (C::REM4 ? KC : 0) + KC : 0;
   constexpr int nA_base = nA_flush + nA_rows + nA_bop;
   constexpr int nA = nA_base + nA_cop;
@@ -534,13 +515,6 @@ __device__ __forceinline__ int wave_stage2(const MfmaParams &P, double *sm, cons
         vbuf[i < NCH ? i : 0] = VO::read(V, i, lane);
       if (i >= 2)
         VO::write(vflush, i - 2, lane, vbuf[i - 2 < NCH ? i - 2 : 0]);
-#ifdef GAR_PROBE_AFF_LINEAR // (timing probe: the bytes of Aff as 16-byte-per-lane linear stores, garbage data)
-      if (i >= 2 && !WIDE) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-          *reinterpret_cast<double2_t *>(&(vflush - M::NR * NX)[2 * (64 * (2 * (i - 2) + u) + lane)]) = vbuf[i - 2 < NCH ? i - 2 : 0];
-      }
-#endif
     } else if (i < nA_flush + nA_rows) { // Rhat, lane = row
       const int j = i - nA_flush;
       a_row[j < NU ? j : 0] = Mm[j * NU + frow];
@@ -828,9 +802,6 @@ __device__ __forceinline__ int wave_stage2(const MfmaParams &P, double *sm, cons
       for (int sc = 0; sc < KC; ++sc)
         Zb[tj][sc] = X[tj][KU + sc];
     }
-#if GAR_COUPLED_RELOAD_C
-    load_cop(); // (again, L2 hits: the operands do not stay in registers across the solve)
-#endif
     GAR_WMARK(22)
     // [kff; zff] -> column 0 of G (rows 0..NK-1): read back one entry per lane row below
     if (li == (SPARE_C ? lcc : 0)) {
@@ -1010,33 +981,21 @@ __device__ __forceinline__ int wave_stage2(const MfmaParams &P, double *sm, cons
       const int i = 16 * ti + lk + 4 * r, j = 16 * tj + li;
       if (i < NX && j < NX) {
         const double v = ti < C::KSF ? S.Fo[tj][ti < C::KSF ? ti : 0][r] : (C::REM4 ? S.FoT[tj][0] : accT[tj][r]);
-#ifndef GAR_PROBE_NO_AFF_STORE // (timing probe: what the 10.4 KB of Aff per stage cost the sweep; results are then wrong)
         if (WIDE)
           stg_b(out, M::fFB + (NK + 16 * ti + 4 * r) * NX + 16 * tj, fbrm, v);
         else
           stg_b(out, M::fFB + 8 * tj * 2 * NR + 2 * (NK + 16 * ti + 4 * r), L.fbl, v);
-#else
-        asm volatile("" ::"v"(v));
-#endif
       }
     } else if (q < nCol) {
       const int sq = q - nRow4; // k-step of F's column tile tj
-      const double *fsrc = FDMA ? Fb : recn; // (F-DMA: the same addressing, of the LDS image)
-      const double v = WaveLane<NX, NU>::fo_in(tj) ? ldg_b(fsrc, 16 * tj * NX + 4 * sq, L.fo0)
-                                                   : ldg_b(fsrc, 4 * sq, L.foX);
+      const double v = WaveLane<NX, NU>::fo_in(tj) ? ldg_b(recn, 16 * tj * NX + 4 * sq, L.fo0)
+                                                   : ldg_b(recn, 4 * sq, L.foX);
       if (sq < 4 * C::KSF)
         S.Fo[tj][(sq >> 2) < C::KSF ? (sq >> 2) : 0][sq & 3] = v;
       else
         S.FoT[tj][(sq - 4 * C::KSF) < C::KST ? (sq - 4 * C::KSF) : 0] = v;
     }
   };
-  if constexpr (FDMA) {
-    // the DMA pieces were the first vector-memory instructions of this stage; gfx9 retires loads and stores in order
-    // on one counter, so "at most GAR_F_DMA_YOUNGER instructions outstanding" implies "the pieces have landed" as long
-    // as at least that many were issued behind them -- the stage issues > 60 (counted in the ISA, Makefile: fdma_check)
-    GAR_WAIT_VMCNT(GAR_F_DMA_YOUNGER);
-    wave_lds_order();
-  }
   GAR_SB;
   int pend_col = -1, pend_q = 0; // column whose stores/loads are being slotted, next op of it
   int sK = 0;
@@ -1046,17 +1005,11 @@ __device__ __forceinline__ int wave_stage2(const MfmaParams &P, double *sm, cons
     for (int s = 0; s < KU; ++s)
 #pragma unroll
       for (int ti = 0; ti < TX; ++ti) {
-#ifdef GAR_PROBE_NO_AFF // (timing probe: ... and its 27 + 3 MFMAs)
-        if (false) {
-        } else if (ti < C::KSF || C::REM4) {
-        } else {
-#else
         if (ti < C::KSF) {
           S.Fo[tj][ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(Bop[ti][s], Kb[tj][s], S.Fo[tj][ti], 0, 0, 0);
         } else if (C::REM4) {
           S.FoT[tj][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(Bop4[s], Kb[tj][s], S.FoT[tj][0], 0, 0, 0);
         } else {
-#endif
           accT[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(Bop[ti][s], Kb[tj][s], accT[tj], 0, 0, 0);
         }
         if (ti < C::KSF || !C::REM4) { // behind a 16x16x4
@@ -1213,7 +1166,7 @@ __device__ __forceinline__ int wave_stage2(const MfmaParams &P, double *sm, cons
   wave_sync();
   GAR_WMARK(14)
   // ---- knot t-1: its Hessian tiles replace H
-  wave_load_b<NX, NU, WaveLane<NX, NU, NC>, (GAR_QR_PACKED && !WIDE)>(recn, L, S);
+  wave_load_b<NX, NU, WaveLane<NX, NU, NC>, !WIDE>(recn, L, S);
   GAR_WMARK(9)
   // ---- Vxx -> HBM is left to the next stage (list A) / to the caller after the last one -----------
   vflush = out + oVxx;

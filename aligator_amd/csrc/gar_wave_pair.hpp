@@ -23,40 +23,9 @@
 #include "gar_wave2.hpp"
 #include "gar_ldl_blocked.hpp"
 
-namespace gar {
-
-// Wide F loads (round 6).  The contraction index of P = V'F and H = W + F^T P -- the NEXT state's index, the rows of
-// F = [A | B] -- is free to be relabelled: MFMA k-step s, lane group lk may stand for ANY row as long as both operands
-// of a product agree.  With row(s, lk) = KS lk + s instead of 4 s + lk a lane's KS operand values of one tile column
-// are KS CONTIGUOUS doubles of a column of the column-major knot block: KS / 2 16-byte loads (global_load_dwordx4)
-// instead of KS 8-byte ones -- 35 instead of 70 load instructions for wave 0 at (56, 24), 21 instead of 42 for wave 1,
-// on a wave whose end-of-stage burst of ~100 loads behind ~40 record stores is what it waits for (gfx9: ONE in-order
-// counter of 63 outstanding memory instructions).  Everything indexed by the next state follows the same relabelling
-// pos -> row: pos = 4 s + lk (the position the hardware's C/D layout gives the accumulators) holds row
-// pi(pos) = KS (pos & 3) + (pos >> 2): the rows of V' read as the A operand of P (so P comes out with its rows in
-// position order and feeds H unchanged), vx' and f in the vector part, the rows of B as the A operand of Aff, the
-// rows of Aff / yff on their way out.  Results: the same sums in the same order per entry (the k-steps visit the
-// rows in another order: last-digit differences against the 8-byte build, none against the record layout).
-// MEASURED AND NOT ADOPTED (round 6; same box, alternating launches, 1 024 distinct device-generated problems, N = 275;
-// profiles/r06_ab_pair_wide_f_loads_and_load_order_not_kept.log): backward 14.45 ms with the 8-byte loads, 14.72 ms
-// with the 16-byte ones, 14.70 ms with those issued in consumption order (GAR_PAIR_ORDER) -- solutions equal to
-// 5e-15.  The number of load instructions is not what the production schedule waits for (the tracing build, whose
-// marks pin the schedule, shows the burst shrink from 23.7 k to 7.9 k cycles on wave 1: the compiler's own placement
-// of the loads had hidden it already).  Both stay available: make variant NAME=pairwide DEFS="-DGAR_PAIR_WIDE_F=1".
-#ifndef GAR_PAIR_WIDE_F
-#define GAR_PAIR_WIDE_F 0
-#endif
-#ifndef GAR_PAIR_ORDER
-#define GAR_PAIR_ORDER 0
-#endif
-// Packed records for the SERIAL wide family (round 6; what the headline family has had since rounds 3 / 4): the knot
-// records keep Q and R as packed lower triangles (gar_layout.h: gar_lower_index; 1 540 + 276 of 9 672 doubles less read
-// per knot at (56, 24) -- the upper triangles never reach a result), the factor records the lower triangle of Vxx,
-// rectangular packed (gar_sym_index: 1 596 instead of 3 136 doubles written per stage and read by the roll-out,
-// gar_forward_wide<.., true>).  The segment-leg kernels (gar_leg_seg.hpp) keep full blocks: PKD = false there.
-#ifndef GAR_PAIR_PACKED
-#define GAR_PAIR_PACKED 1
-#endif
+// ---- compile-time switches of this file (besides -DGAR_TRACE, the cycle stamps of the `make trace` build):
+// tests/test_ldl_blocked.py builds the emulator with non-default values of all three and checks the result against
+// the oracle.
 // The 24 x 24 register L D L^T of Rhat (276 broadcast-FMA pairs through v_readlane: 10.6 - 11.8 k cycles of the stage
 // with the other wave idle) as TWO 12-column panels on DPP broadcasts + one MFMA trailing update
 // (gar_ldl_blocked.hpp).  Shapes whose Rhat fits one DPP row (NU <= 16) keep the register version.
@@ -83,21 +52,18 @@ namespace gar {
 #ifndef GAR_PAIR_UNEVEN
 #define GAR_PAIR_UNEVEN 1
 #endif
-#ifndef GAR_PAIR_EARLY_LOADS
-#define GAR_PAIR_EARLY_LOADS 1
-#endif
-#ifndef GAR_WIDE_FWD_PIPELINED
-#define GAR_WIDE_FWD_PIPELINED 1
-#endif
+
+namespace gar {
+
+// Packed records for the SERIAL wide family (round 6; what the headline family has had since rounds 3 / 4): the knot
+// records keep Q and R as packed lower triangles (gar_layout.h: gar_lower_index; 1 540 + 276 of 9 672 doubles less read
+// per knot at (56, 24) -- the upper triangles never reach a result), the factor records the lower triangle of Vxx,
+// rectangular packed (gar_sym_index: 1 596 instead of 3 136 doubles written per stage and read by the roll-out,
+// gar_forward_wide<.., true>).  The segment-leg kernels (gar_leg_seg.hpp) keep full blocks: PKD = false there.
 
 template <int NX, int NU> struct PairCfg {
   using C = WaveCfg<NX, NU, 0>;
   static constexpr int SPLIT = C::TW / 2;
-  // (the wide shapes only: their records carry fb row-major; an even number of k-steps keeps every piece 16-byte aligned)
-  static constexpr bool PX = GAR_PAIR_WIDE_F && MfmaCfg<NX, NU, 0>::WIDE && (C::KS % 2 == 0) && (NX % 4 == 0);
-  // next-state row that k-step s, lane group lk stands for / that accumulator position pos holds
-  __host__ __device__ static constexpr int krow(int s, int lk) { return PX ? C::KS * lk + s : 4 * s + lk; }
-  __host__ __device__ static constexpr int prow(int pos) { return PX ? C::KS * (pos & 3) + (pos >> 2) : pos; }
   static constexpr int oHq = (C::total + 1) & ~1;          // [qhat; rhat], one entry per index
   static constexpr int oFlag2 = oHq + ((C::NW + 1) & ~1);  // verdict of the factorisation (int)
   static constexpr bool BLK = GAR_PAIR_BLOCKED_LDL && NU > 16 && NU % 4 == 0;
@@ -106,7 +72,7 @@ template <int NX, int NU> struct PairCfg {
   // the columns >= NX / 16
   static constexpr bool UNEVEN = GAR_PAIR_UNEVEN && MfmaCfg<NX, NU, 0>::WIDE && (NX >> 4) > SPLIT;
   static constexpr int SPLIT1 = UNEVEN ? (NX >> 4) : SPLIT;
-  static constexpr bool EARLY = UNEVEN && (GAR_PAIR_EARLY_LOADS != 0) && !GAR_PAIR_ORDER;
+  static constexpr bool EARLY = UNEVEN;
   static constexpr int nXq = UNEVEN ? (SPLIT1 - SPLIT) * C::TX * 4 * 64 : 0; // hand-off of the Qhat tiles of the columns that change hands
   static constexpr int oXq = oLdl + (BLK ? LdlBlockedLds<NU>::total : 0);
   static constexpr int total = oXq + nXq;
@@ -119,27 +85,6 @@ template <int NX, int NU> struct PairCfg {
 template <int NX, int NU, class LANE>
 __device__ __forceinline__ void pair_load_F(const double *rec, const LANE &L, WaveStage<NX, NU> &S, int t, int lane) {
   using C = WaveCfg<NX, NU>;
-  using PC = PairCfg<NX, NU>;
-  if constexpr (PC::PX) {
-    // rows KS lk .. KS lk + KS - 1 of column 16 t + li: KS / 2 pieces of 16 bytes
-    using M = MfmaCfg<NX, NU, 0>;
-    const int li = lane & 15, lk = lane >> 4;
-    const int col = (16 * t + li) < C::NW ? (16 * t + li) : C::NW - 1;
-    const unsigned lb = 8u * (unsigned)(M::kA + (WaveLane<NX, NU>::fo_in(t) ? li : col) * NX + C::KS * lk);
-    const double *base = rec + (WaveLane<NX, NU>::fo_in(t) ? 16 * t * NX : 0);
-#pragma unroll
-    for (int s = 0; s < C::KS; s += 2) {
-      const double2_t v = *reinterpret_cast<const double2_t *>(reinterpret_cast<const char *>(base + s) + lb);
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        if (s + e < 4 * C::KSF)
-          S.Fo[t][(s + e) >> 2][(s + e) & 3] = v[e];
-        else
-          S.FoT[t][s + e - 4 * C::KSF] = v[e];
-      }
-    }
-    return;
-  }
 #pragma unroll
   for (int s = 0; s < C::KS; ++s) {
     const double v = WaveLane<NX, NU>::fo_in(t) ? ldg_b(rec, 16 * t * NX + 4 * s, L.fo0) : ldg_b(rec, 4 * s, L.foX);
@@ -165,7 +110,7 @@ __device__ __forceinline__ void pair_load_H(const double *rec, const LANE &L, Wa
       S.Hc[ti][tj][r] = 0.0;
   }
 }
-// PART (uneven first half, GAR_PAIR_EARLY_LOADS): 0 = everything; 1 = only what this wave's registers can take right
+// PART (uneven first half, PairCfg::EARLY): 0 = everything; 1 = only what this wave's registers can take right
 // behind its FIRST half -- wave 0: F's tile columns >= SPLIT (its Aff needs the first SPLIT only) and the Hessian tiles of
 // the state columns it computed for wave 1; wave 1: F's pure control column(s) and the Rhat-only tile(s) --; 2 = the rest.
 // The workgroup barriers of the stage are fences the compiler does not move loads across: without the split every one of
@@ -178,29 +123,6 @@ __device__ __forceinline__ void pair_load(const double *rec, const LANE &L, Wave
   [[maybe_unused]] auto early_H = [](int ti, int tj) {
     return PC::UNEVEN && (W == 0 ? PC::owner(tj) == 1 : (16 * tj >= NX && 16 * ti >= NX));
   };
-#if GAR_PAIR_ORDER
-  // in the order the next stage consumes them (loads return in order: its first products wait for the first pieces
-  // only): tile columns from the last one down -- F(:, tj) feeds P(:, tj), then H(ti, tj), ti = tj .., wants F(:, ti)
-  // and its Hessian tile
-  bool have[C::TW] = {};
-#pragma unroll
-  for (int tj = C::TW - 1; tj >= 0; --tj) {
-    if (PC::owner1(tj) != W)
-      continue;
-#pragma unroll
-    for (int ti = tj; ti < C::TW; ++ti) {
-      if (!have[ti]) {
-        pair_load_F<NX, NU>(rec, L, S, ti, lane);
-        have[ti] = true;
-      }
-      pair_load_H<NX, NU, QP>(rec, L, S, ti, tj);
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < C::TW; ++t) // (F columns a wave needs for Aff only)
-    if (!have[t] && !(W == 1 && t < PC::SPLIT))
-      pair_load_F<NX, NU>(rec, L, S, t, lane);
-#else
 #pragma unroll
   for (int t = 0; t < C::TW; ++t)
     if (!(W == 1 && t < PC::SPLIT) && (PART == 0 || (PART == 1) == early_F(t)))
@@ -211,7 +133,6 @@ __device__ __forceinline__ void pair_load(const double *rec, const LANE &L, Wave
     for (int tj = 0; tj <= ti; ++tj)
       if (PC::owner1(tj) == W && (PART == 0 || (PART == 1) == early_H(ti, tj)))
         pair_load_H<NX, NU, QP>(rec, L, S, ti, tj);
-#endif
 }
 
 template <int NX, int NU, int W, bool PKD = false>
@@ -252,12 +173,12 @@ __device__ __forceinline__ void pair_stage(const MfmaParams &P, double *sm, cons
   double vxs[KS], fs[KS];
 #pragma unroll
   for (int s = 0; s < KS; ++s)
-    vxs[s] = PC::PX ? vn[KS * lk + s] : vn[4 * s + lk];
+    vxs[s] = vn[4 * s + lk];
   {
-    const unsigned lkb = 8u * (unsigned)(PC::PX ? KS * lk : lk);
+    const unsigned lkb = 8u * (unsigned)lk;
 #pragma unroll
     for (int s = 0; s < KS; ++s)
-      fs[s] = ldg_b(rec, M::kf + (PC::PX ? s : 4 * s), lkb);
+      fs[s] = ldg_b(rec, M::kf + 4 * s, lkb);
   }
   double qrv[TW]; // [q; r] entries of this wave's columns: issued here, used after the products
 #pragma unroll
@@ -280,9 +201,8 @@ __device__ __forceinline__ void pair_stage(const MfmaParams &P, double *sm, cons
       const double bq = S.fo(tj, s);
 #pragma unroll
       for (int tm = 0; tm < TX; ++tm) {
-        // (PX: the row of V' whose product lands on accumulator position 16 tm + li, the column of k-step s)
-        const int ic = (16 * tm + li) < NX ? PC::prow(16 * tm + li) : NX - 1;
-        Pt[tm] = __builtin_amdgcn_mfma_f64_16x16x4f64(V[ic * PK + PC::krow(s, lk)], bq, Pt[tm], 0, 0, 0);
+        const int ic = (16 * tm + li) < NX ? (16 * tm + li) : NX - 1;
+        Pt[tm] = __builtin_amdgcn_mfma_f64_16x16x4f64(V[ic * PK + 4 * s + lk], bq, Pt[tm], 0, 0, 0);
       }
     }
 #pragma unroll
@@ -307,17 +227,12 @@ __device__ __forceinline__ void pair_stage(const MfmaParams &P, double *sm, cons
   for (int ti = 0; ti < TX; ++ti)
 #pragma unroll
     for (int s = 0; s < KU; ++s)
-      if constexpr (PC::PX) { // B(pi(16 ti + li), 4 s + lk): the row whose Aff lands on accumulator position 16 ti + li
-        const int p = 16 * ti + li, row = p < NX ? PC::prow(p) : NX - 1;
-        Bop[ti][s] = ldg_b(rec, M::kB + 4 * s * NX, 8u * (unsigned)(lk * NX + row));
-      } else {
-        Bop[ti][s] = WaveLane<NX, NU>::x_in(ti) ? ldg_b(rec, 4 * s * NX + 16 * ti, L.bop0) : ldg_b(rec, 4 * s * NX, L.bopX);
-      }
+      Bop[ti][s] = WaveLane<NX, NU>::x_in(ti) ? ldg_b(rec, 4 * s * NX + 16 * ti, L.bop0) : ldg_b(rec, 4 * s * NX, L.bopX);
   double fyf[TX];
 #pragma unroll
   for (int ti = 0; ti < TX; ++ti)
     if (PC::owner(ti) == W) {
-      const int i = 16 * ti + li, ic = i < NX ? PC::prow(i) : NX - 1;
+      const int i = 16 * ti + li, ic = i < NX ? i : NX - 1;
       fyf[ti] = ldg_b(rec, M::kf, 8u * (unsigned)ic);
     }
   GAR_PMARK(1)
@@ -538,7 +453,7 @@ __device__ __forceinline__ void pair_stage(const MfmaParams &P, double *sm, cons
       const double yf = fyf[ti] + rows_sum(a, lane);
       const double vxv = hqv[ic] + rows_sum(c, lane);
       if (lk == 0 && i < NX) {
-        out[M::fFF + NK + PC::prow(i)] = yf; // (PX: position i holds next-state row pi(i); vx is indexed by THIS state)
+        out[M::fFF + NK + i] = yf;
         out[ovx + i] = vxv;
         vn[i] = vxv;
       }
@@ -571,9 +486,7 @@ __device__ __forceinline__ void pair_stage(const MfmaParams &P, double *sm, cons
         if (16 * ti + 4 * r < NX) {
           if (i < NX && j < NX) {
             const double v = ti < C::KSF ? S.Fo[tj][ti < C::KSF ? ti : 0][r] : accT[r];
-            if (PC::PX) // position 16 ti + 4 r + lk holds row KS lk + 4 ti + r
-              stg_b(out, M::fFB + (NK + 4 * ti + r) * NX + 16 * tj, 8u * (unsigned)(KS * lk * NX + li), v);
-            else if (WIDE)
+            if (WIDE)
               stg_b(out, M::fFB + (NK + 16 * ti + 4 * r) * NX + 16 * tj, fbrm, v);
             else
               stg_b(out, M::fFB + 8 * tj * 2 * NR + 2 * (NK + 16 * ti + 4 * r), L.fbl, v);
@@ -630,7 +543,7 @@ __device__ __forceinline__ void pair_stage(const MfmaParams &P, double *sm, cons
   // ---- Vxx -> HBM, 16 B per lane, the chunks alternate between the waves: column-major and symmetric for the wide
   // shapes, the packed lower triangle (gar_layout.h) where the roll-out is gar_forward_mfma ----
   {
-    using VO = VxxOut<NX, PKD || (GAR_VXX_PACKED && !WIDE), PK>;
+    using VO = VxxOut<NX, PKD || !WIDE, PK>;
 #pragma unroll
     for (int q = W; q < VO::NCH; q += 2)
       VO::write(out + oVxx, q, lane, VO::read(V, q, lane));
@@ -663,7 +576,7 @@ __global__ void __launch_bounds__(128, (NX + NU > 64) ? 1 : 2) gar_backward_pair
       const int j = e / NX, i = e - j * NX;
       const double v = (i >= j) ? rec[M::tQ + e] : rec[M::tQ + i * NX + j];
       V[i * PK + j] = v;
-      if (!PKD && (M::WIDE || !GAR_VXX_PACKED))
+      if (!PKD && M::WIDE)
         out[M::tVxx + e] = v;
       else if (i >= j)
         out[M::tVxx + gar_sym_index(1, NX, i, j)] = v; // (packed lower triangle: gar_layout.h)
@@ -679,7 +592,7 @@ __global__ void __launch_bounds__(128, (NX + NU > 64) ? 1 : 2) gar_backward_pair
   // one loop per wave: each keeps only ITS tiles in registers across the stages (a common loop would
   // carry the union of both waves' state through either path)
 #if GAR_PAIR_REFRESH_LANE
-  // (as in the coupled constrained stage, gar_wave.hpp GAR_COUPLED_REFRESH_LANE: the lane offsets re-derived per stage
+  // (as in the coupled constrained stage, gar_wave.hpp: the lane offsets re-derived per stage
   // from a lane index the compiler cannot prove loop-invariant, instead of ~100 values parked in accumulator registers
   // and copied back at every use)
   if (wave == 0) {
@@ -747,7 +660,6 @@ __global__ void __launch_bounds__(64) gar_forward_wide(MfmaFwdParams P) {
     sol[lane] = xs;
   for (int e = lane; e < P.nc0; e += 64)
     sol[P.sol_l + e] = io[NX + e]; // lbd0
-#if GAR_WIDE_FWD_PIPELINED
   if constexpr (VPACK) {
     // The packed roll-out, software-pipelined (round 6): a stage's operands are two groups -- G1 = its [kff | K],
     // [yff | Aff] rows (u, x' need them), G2 = the NEXT stage's packed Vxx', vx' (lbd' needs them) -- and each group is
@@ -825,28 +737,19 @@ __global__ void __launch_bounds__(64) gar_forward_wide(MfmaFwdParams P) {
     }
     return;
   }
-#endif
   for (int t = 0; t < N; ++t) {
     const double *rec = fac + P.slot(t) * P.fac_rec;
     const double *recn = (t + 1 < N) ? fac + P.slot(t + 1) * P.fac_rec : fac + P.fac_offN;
     const int oVn = (t + 1 < N) ? M::fVxx : M::tVxx, ovn = (t + 1 < N) ? M::fvx : M::tvx;
-    double2_t aff[NX / 2], kro[NX / 2], vrow[VPACK ? 1 : NX / 2], vp[VPACK ? VO::NCH : 1];
+    double2_t aff[NX / 2], kro[NX / 2], vrow[NX / 2];
 #pragma unroll
     for (int m = 0; m < NX / 2; ++m) {
       kro[m] = *reinterpret_cast<const double2_t *>(rec + M::fFB + iK * NX + 2 * m);
       aff[m] = *reinterpret_cast<const double2_t *>(rec + M::fFB + (NU + iA) * NX + 2 * m);
     }
-    if constexpr (VPACK) {
 #pragma unroll
-      for (int q = 0; q < VO::NCH; ++q) {
-        const int e = 64 * q + lane, ec = (64 * q + 63 < VO::NP2 || e < VO::NP2) ? e : VO::NP2 - 1;
-        vp[q] = *reinterpret_cast<const double2_t *>(recn + oVn + 2 * ec);
-      }
-    } else {
-#pragma unroll
-      for (int m = 0; m < NX / 2; ++m)
-        vrow[m] = *reinterpret_cast<const double2_t *>(recn + oVn + iA * NX + 2 * m);
-    }
+    for (int m = 0; m < NX / 2; ++m)
+      vrow[m] = *reinterpret_cast<const double2_t *>(recn + oVn + iA * NX + 2 * m);
     const double kff = rec[M::fFF + iK], yff = rec[M::fFF + NU + iA], vxn = recn[ovn + iA];
     double u0 = kff, u1 = 0.0, x0 = yff, x1 = 0.0;
 #pragma unroll
@@ -863,31 +766,10 @@ __global__ void __launch_bounds__(64) gar_forward_wide(MfmaFwdParams P) {
     if (lane < NX)
       sol[(t + 1) * NX + lane] = xn;
     double l0 = vxn, l1 = 0.0; // lbd' = vx' + Vxx' x'  (:369-371)
-    if constexpr (VPACK) {
-      wave_sync(); // (the previous stage's row reads are done)
 #pragma unroll
-      for (int q = 0; q < VO::NCH; ++q) {
-        const int e = 64 * q + lane;
-        if (64 * q + 63 < VO::NP2 || e < VO::NP2)
-          *reinterpret_cast<double2_t *>(&vb[2 * e]) = vp[q];
-      }
-      wave_sync();
-      // row iA of the symmetric matrix from its packed lower triangle (gar_sym_index): elements (iA, j), j <= iA, at
-      // cj + iA; (j, iA), j > iA, at lowbase + j
-      const int lowbase = 2 * iA < NX ? iA * NX : (NX - 1 - iA) * (NX + 1) + 1;
-#pragma unroll
-      for (int j = 0; j < NX; j += 2) {
-        const int c0 = 2 * j < NX ? j * NX : (NX - 1 - j) * (NX + 1) + 1;
-        const int c1 = 2 * (j + 1) < NX ? (j + 1) * NX : (NX - 2 - j) * (NX + 1) + 1;
-        l0 = __builtin_fma(vb[iA >= j ? c0 + iA : lowbase + j], lane_bcast(xn, j), l0);
-        l1 = __builtin_fma(vb[iA >= j + 1 ? c1 + iA : lowbase + j + 1], lane_bcast(xn, j + 1), l1);
-      }
-    } else {
-#pragma unroll
-      for (int m = 0; m < NX / 2; ++m) {
-        l0 = __builtin_fma(vrow[m].x, lane_bcast(xn, 2 * m), l0);
-        l1 = __builtin_fma(vrow[m].y, lane_bcast(xn, 2 * m + 1), l1);
-      }
+    for (int m = 0; m < NX / 2; ++m) {
+      l0 = __builtin_fma(vrow[m].x, lane_bcast(xn, 2 * m), l0);
+      l1 = __builtin_fma(vrow[m].y, lane_bcast(xn, 2 * m + 1), l1);
     }
     if (lane < NX)
       sol[P.sol_l + P.nc0 + t * NX + lane] = l0 + l1;

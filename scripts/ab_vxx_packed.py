@@ -1,6 +1,8 @@
-"""A/B on ONE box, alternating launches: the serial (36, 12) sweep with the packed lower triangle of Vxx in its
-factor records (libgar_hip.so) against the full block (libgar_hip_vxxfull.so: make -C aligator_amd/csrc vxxfull).
-Backward and forward kernel times from the library's HIP events, batch 4 096, N = 256."""
+"""A/B on ONE box, alternating launches: the serial (36, 12) sweep of two builds of the library, e.g. the production
+library against a `make -C aligator_amd/csrc sweepvariant NAME=x DEFS=...` build.
+Usage: ab_vxx_packed.py BATCH name=lib name=lib (library file names under aligator_amd/).
+Backward and forward kernel times from the library's HIP events, N = 256.  (The name is historical: the first A/B run
+with it was packed against full Vxx records.)"""
 import ctypes as C, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -8,12 +10,11 @@ sys.path.insert(0, ROOT)
 import torch
 from aligator_amd import synth_device
 from aligator_amd.gar import BatchedRiccatiSolver
-nx, nu, N, batch = 36, 12, 256, int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+if len(sys.argv) != 4 or any("=" not in a for a in sys.argv[2:]):
+    sys.exit(__doc__)
+nx, nu, N, batch = 36, 12, 256, int(sys.argv[1])
 dims = [(nx, nu, 0, nx, 0)] * N + [(nx, 0, 0, nx, 0)]
-libs = {"packed": os.path.join(ROOT, "aligator_amd", "libgar_hip.so"),
-        "full": os.path.join(ROOT, "aligator_amd", "libgar_hip_vxxfull.so")}
-if len(sys.argv) > 2:   # any two builds: name=path name=path
-    libs = {a.split("=")[0]: os.path.join(ROOT, "aligator_amd", a.split("=")[1]) for a in sys.argv[2:]}
+libs = {a.split("=")[0]: os.path.join(ROOT, "aligator_amd", a.split("=")[1]) for a in sys.argv[2:]}
 solvers = {}
 for name, path in libs.items():
     s = BatchedRiccatiSolver(dims, nx, batch=batch, num_legs=1, device=0, lib_path=path)
