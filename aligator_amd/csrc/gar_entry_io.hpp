@@ -132,8 +132,7 @@ int gar_hip_condensed_resolved(gar_hip_solver *s, int b, int *out) {
   GAR_MULTI(s, gar_hip_condensed_resolved(s->multi->subs[0], b, out));
   if (s->num_legs < 2 || !out)
     return fail(GAR_HIP_ERR_ARG, "condensed info needs leg mode");
-  const int64_t nblk = 2 * s->num_legs, bs = (int64_t)s->nxb * s->nxb;
-  const double *info = s->d_cscratch + (int64_t)b * s->cscratch_doubles + 4 * nblk * bs + 4 * nblk * s->nxb;
+  const double *info = s->d_cscratch + (int64_t)b * s->cscratch_doubles + cond_info_off(s);
   double v = 0.0;
   if (int rc = d2h(s, &v, info + 3, 1))
     return rc;
@@ -149,8 +148,7 @@ int gar_hip_condensed_backward_error(gar_hip_solver *s, int b, double *out) {
   GAR_MULTI(s, gar_hip_condensed_backward_error(s->multi->subs[0], b, out));
   if (s->num_legs < 2 || !out)
     return fail(GAR_HIP_ERR_ARG, "condensed info needs leg mode");
-  const int64_t nblk = 2 * s->num_legs, bs = (int64_t)s->nxb * s->nxb;
-  const double *info = s->d_cscratch + (int64_t)b * s->cscratch_doubles + 4 * nblk * bs + 4 * nblk * s->nxb;
+  const double *info = s->d_cscratch + (int64_t)b * s->cscratch_doubles + cond_info_off(s);
   double v[3] = {0.0, 0.0, 0.0};
   if (int rc = d2h(s, v, info, 3))
     return rc;

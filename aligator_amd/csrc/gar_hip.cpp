@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -35,6 +36,7 @@
 #include "gar_fold.hpp"
 #include "gar_cstr_seg_api.hpp"
 #include "gar_leg_seg.hpp"
+#include "gar_host.hpp"
 
 namespace gar { // instantiated in gar_wave_sweep.cpp (its own translation unit, its own code-generation flags)
 #define GAR_SWEEP_EXTERN(NX, NU)                                                                                        \
@@ -179,59 +181,36 @@ struct DeviceGuard {
 
 struct gar_multi;
 
-struct gar_hip_solver {
+struct gar_hip_solver : gar::HostLayout, gar::KernelBinding {
   // gar_hip_multi_create: this object holds the layout only (no device memory); `multi` owns the per-device solvers
   gar_multi *multi = nullptr;
-  int device = 0, horizon = 0, nc0 = 0, batch = 0;
-  int num_legs = 1, leg_begin = 0, leg_end = 1;
+  int device = 0, batch = 0;
+  int leg_begin = 0, leg_end = 1;
   int world = 1, rank = 0; // horizon sharding: this solver owns legs [rank J / W, (rank + 1) J / W)
-  std::vector<gar_stage_meta> meta;
-  std::vector<int32_t> dims5; // dimensions of the DEVICE records (= the caller's unless padded)
   // Padding onto a specialised kernel family happens HERE, behind the C ABI (riccati-base.hpp:13-37 is what
   // binds: the caller passes the knots' own dimensions).  A uniform, unconstrained, unparameterised problem whose
   // (nx, nu) has no kernel of its own runs on the smallest specialised shape (NX >= nx, NU >= nu) with DUMMY
   // controls (R = I, S = 0, B = 0, r = 0) and DUMMY states (Q = I, A = 0, f = 0, pinned to zero by extra rows
   // [0 -I] x0 = 0 of the initial constraint): both solve to exactly zero, decouple from the real variables, and
   // are stripped from every result.  user_* = what the caller passed; `ulay` = the layout of the caller-facing
-  // records (packed problem, solution, gains) when they differ from the device's.
+  // records (packed problem, solution, gains) when they differ from the device's (caller_layout).
   std::vector<int32_t> user_dims5;
   int user_nc0 = 0;
   bool padded = false;
   int unx = 0, unu = 0, pnx = 0, pnu = 0; // caller's / device (nx, nu) of the uniform stages
-  gar_hip_solver *ulay = nullptr;         // host-only layout object (no device memory), owned
-  // Constrained knots (nc > 0) in leg mode on the unconstrained wave-leg kernels (gar_fold.hpp): `flay` = the
-  // layout of the folded problem (same knots, nc = 0), d_prob2 / d_fac2 / d_meta2 its device records.  Problems
-  // with D != 0 are flagged on the device (d_status + batch + 4) and taken by the generic leg kernels.
-  // Segment legs (gar_leg_seg.hpp): leg mode for shapes with a serial stage kernel but no wave-leg family -- the
-  // plain part of every leg by that kernel into scratch records (flay: the same knots, nth = 0; d_fac2), the
-  // parameter part by the generic matrix recursion, which writes the caller-visible records and the tuples
-  void (*seg_bwd_kernel)(gar::MfmaParams, int, int) = nullptr;
-  void (*seg_fwd_kernel)(gar::GenericParams) = nullptr; // its roll-out (gar_forward_wide_leg), leg mode
-  int seg_lds_doubles = 0;
-  bool fold = false, fold_expanded = false, coupled_known = false;
-  // ... unless the shape has the constrained segment legs (gar_cstr_seg.hpp, round 6): then the flagged problems run
-  // on the serial constrained chain's stage kernels, leg by leg, + a parameter recursion; the knots keep Q, R packed
-  // (qr_packed), the plain part's records go to the flagged problem's slice of d_fac2, d_cseg_resume holds the chain's
-  // hand-over knot per (problem, local leg)
-  bool cseg_on = false;
+  std::unique_ptr<gar::HostLayout> ulay;
+  // `flay` = the layout of the folded problem (KernelBinding::fold: same knots, nc = 0) or of the segment legs'
+  // scratch records (seg_bwd_kernel: same knots, serial); d_prob2 / d_fac2 / d_meta2 its device records
+  std::unique_ptr<gar::HostLayout> flay;
+  bool fold_expanded = false, coupled_known = false;
   bool mu_divides = false; // some knot's solve divides by mueq outright (see gar_hip_backward_legs_async)
   bool any_nc = false;     // some knot carries constraints: a non-finite mueq is refused (ibid.)
-  gar::CsegKernels cseg;
   int *d_cseg_resume = nullptr;
-  gar_hip_solver *flay = nullptr;
   double *d_prob2 = nullptr, *d_fac2 = nullptr;
   gar_stage_meta *d_meta2 = nullptr;
   double fold_mueq = 0.0;
   std::vector<int> h_coupled;
   gar_stage_meta *d_meta = nullptr;
-  int64_t prob_doubles = 0, fac_doubles = 0, sol_doubles = 0, init_doubles = 0;
-  int64_t G0_off = 0, g0_off = 0;
-  int64_t sol_x = 0, sol_u = 0, sol_v = 0, sol_l = 0; // base offsets of xs/us/vs/lbdas
-  int nx0 = 0, nth0 = 0, n0 = 0;
-  // MPC cycling as a ring (uniform serial problems): logical stage t < horizon lives in record slot
-  // (t + ring0) mod horizon; meta[t].in_off / fac_off follow, the records never move
-  int ring0 = 0;
-  int64_t uni_in0 = 0, uni_in_rec = 0, uni_fac_rec = 0; // slot 0 and the record pitches (layout time)
   double *d_prob = nullptr, *d_fac = nullptr, *d_sol = nullptr, *d_init = nullptr;
   double *d_theta = nullptr;
   int *d_status = nullptr;
@@ -260,60 +239,18 @@ struct gar_hip_solver {
   std::vector<std::vector<std::pair<int64_t, int64_t>>> dirty_iv;
   hipStream_t own_stream = nullptr, stream = nullptr;
   gar::LdsPlan lds{};
-  // RiccatiSolverDense (gar_dense.hpp): factor records carry nu+nc+2*nx2 gain rows
-  bool dense = false;
   gar::DensePlan dense_lds{};
-  int cond_lds_doubles = 0;
-  std::string kernel_name = "generic";
   int last_failed = 0;
-  // specialised backward kernel (gar_mfma.hpp), null = generic
-  void (*mfma_kernel)(gar::MfmaParams) = nullptr;
-  void (*mfma_fwd_kernel)(gar::MfmaFwdParams) = nullptr;
-  size_t mfma_fwd_lds_bytes = 0; // gar_forward_mfma: the packed Vxx' of a stage goes through LDS
-  int mfma_lds_doubles = 0;
-  // one-wave-per-problem backward kernel (gar_wave.hpp), preferred when bound
-  void (*wave_kernel)(gar::MfmaParams, int) = nullptr;
-  void (*wave_coupled_kernel)(gar::MfmaParams, int) = nullptr; // constrained sweeps: the second ...
-  void (*wave_bk_kernel)(gar::MfmaParams, int) = nullptr;      // ... and the third kernel of the chain
-  int wave_lds_doubles = 0, waves_per_block = 1;
-  int wave_block_threads = 64; // 128: two waves per problem (gar_wave_pair.hpp)
-  bool fb_t2 = false;      // factor records keep fb / fth in the fbT2 device order (gar_mfma.hpp)
-  bool vxx_packed = false; // ... and the lower triangle of Vxx, packed (gar_layout.h: the serial one-wave family)
-  bool wide_vxx_packed = false; // (set by bind_wide: the serial two-wave family with packed records)
-  bool qr_packed = false;  // knots t < N keep Q and R as packed lower triangles (gar_layout.h: the headline sweep)
   std::string lds_error;   // the generic kernels do not fit a CU's LDS (fatal unless a specialised family serves the shape)
-  bool wave_fused_init = false;
-  bool init_closed = true; // closed-form initial stage when G0 = +-I (GAR_HIP_INIT=bk: always factorise)
-  // one-wave-per-(problem, leg) kernels (gar_wave_leg.hpp), bound for uniform leg-mode problems
-  void (*leg_bwd_kernel)(gar::LegParams) = nullptr;
-  void (*leg_tuple_kernel)(gar::LegParams) = nullptr;
-  void (*leg_fwd_kernel)(gar::LegParams) = nullptr;
-  void (*leg_collapse_kernel)(const gar_stage_meta *, double *, long long, int, const int *, int) = nullptr;
-  int leg_lds_doubles = 0, leg_waves = 1;
-  void (*cond_wave_kernel)(gar::CondensedParams) = nullptr;
-  int cond_wave_lds_doubles = 0;
-  // block cyclic reduction of the condensed system (gar_cyclic.hpp), preferred when bound
-  void (*cyc_setup_kernel)(gar::CyclicParams) = nullptr;
-  void (*cyc_reduce_kernel)(gar::CyclicParams) = nullptr;
-  void (*cyc_top_kernel)(gar::CyclicParams) = nullptr;
-  void (*cyc_backlevel_kernel)(gar::CyclicParams) = nullptr;
-  void (*cyc_recover_kernel)(gar::CyclicParams) = nullptr;
-  int cyc_lds_doubles = 0;
-  int cyc_block_doubles = 0; // one NX x NX block of the cyclic-reduction kernels (gar_cyclic_recover's LDS)
   long long *d_trace = nullptr; // 64 cycle stamps (debug)
+  long long *d_deriv_off = nullptr; // device-resident updateLQSubproblem: HostLayout::deriv_off on the device
+  // bulk read-back (gar_hip_fetch_results): HostLayout::gain_off on the device, the device gather buffer and the
+  // pinned host buffer [solution | ff_all | fb_all] of one problem
+  long long *d_gain_off = nullptr;
+  double *d_gains = nullptr, *h_results = nullptr;
   // optional per-kernel timing of the sweep (bench.py's roofline figure): HIP events recorded on
   // the launch stream around the backward sweep kernel, the initial-stage kernel and the forward
   // sweep kernel of the LAST backward/forward calls
-  // device-resident updateLQSubproblem: layout of one problem's derivative buffer
-  std::vector<long long> deriv_off; // per stage
-  long long deriv_doubles = 0, d_G0 = 0, d_g0 = 0, d_iH = 0;
-  long long *d_deriv_off = nullptr;
-  // bulk read-back (gar_hip_fetch_results): per-stage offsets inside ff_all / fb_all, the device
-  // gather buffer and the pinned host buffer [solution | ff_all | fb_all] of one problem
-  std::vector<long long> gain_off; // 2 per stage
-  long long ff_all_doubles = 0, fb_all_doubles = 0;
-  long long *d_gain_off = nullptr;
-  double *d_gains = nullptr, *h_results = nullptr;
   bool timing = false;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   // gar_hip_prefetch_gains: the bulk read-back of the gains started right behind the backward sweep on a second
@@ -333,11 +270,6 @@ struct gar_hip_solver {
   // OTHER half leaves free on every SIMD (gar_forward_lean.hpp): B(h0) | F(h0) + B(h1) | F(h1) + B'(h0) | ...
   int pipe_halves = 0;                 // 0: off
   int pipe_requested = 0;              // what the caller last asked gar_hip_set_pipeline for (a rebuild re-validates it)
-  void (*lean_fwd_kernel)(gar::MfmaFwdParams, int) = nullptr;
-  void (*wave_half_kernel)(gar::MfmaParams, int) = nullptr; // the backward sweep under its half-batch launch name
-  size_t lean_fwd_used = 0;            // LDS the kernel uses
-  size_t lean_fwd_lds_bytes = 0;       // what the launch ASKS for (> half a CU: one workgroup per CU), see pipe_plan
-  int wave_lds_doubles_small = 0;      // the backward launch without the fused initial stage's kkt0 overlay
   hipStream_t pipe_stream[2] = {nullptr, nullptr};
   hipEvent_t pipe_evB[2] = {nullptr, nullptr}, pipe_evF[2] = {nullptr, nullptr}, pipe_evFork = nullptr;
   hipEvent_t pipe_evT[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}}; // timing
@@ -354,28 +286,28 @@ struct gar_hip_solver {
 namespace {
 
 // ---- layout ---------------------------------------------------------------
-int build_layout(gar_hip_solver *s) {
-  const int N = s->horizon;
-  s->meta.assign(N + 1, gar_stage_meta{});
+int build_layout(gar::HostLayout &s) {
+  const int N = s.horizon;
+  s.meta.assign(N + 1, gar_stage_meta{});
   std::vector<int> leg_of(N + 1, 0), nth_eff(N + 1, 0), flags(N + 1, 0);
   for (int t = 0; t <= N; ++t) {
-    const int32_t *d = &s->dims5[5 * t];
+    const int32_t *d = &s.dims5[5 * t];
     if (d[0] < 0 || d[1] < 0 || d[2] < 0 || d[3] < 0 || d[4] < 0 || d[0] == 0)
       return fail(GAR_HIP_ERR_ARG, "negative or zero state dimension");
     nth_eff[t] = d[4];
     flags[t] = d[4] > 0 ? GAR_KNOT_HAS_PARAM : 0;
   }
-  if (s->num_legs > 1) {
+  if (s.num_legs > 1) {
     // ParallelRiccatiSolver::initialize (parallel-solver.hxx:51-82)
-    for (int i = 0; i < s->num_legs; ++i) {
+    for (int i = 0; i < s.num_legs; ++i) {
       int i0, i1;
-      gar_get_work(N, i, s->num_legs, &i0, &i1);
+      gar_get_work(N, i, s.num_legs, &i0, &i1);
       if (i1 <= i0)
         return fail(GAR_HIP_ERR_ARG, "more legs than stages");
-      const bool last_leg = (i == s->num_legs - 1);
-      const int nth = s->dims5[5 * (i1 - 1) + 3]; // nx2 of the leg's last knot
+      const bool last_leg = (i == s.num_legs - 1);
+      const int nth = s.dims5[5 * (i1 - 1) + 3]; // nx2 of the leg's last knot
       for (int t = i0; t < i1; ++t) {
-        if (s->dims5[5 * t + 4] != 0)
+        if (s.dims5[5 * t + 4] != 0)
           return fail(GAR_HIP_ERR_UNSUPPORTED,
                       "leg mode on a user-parameterised problem is not supported");
         leg_of[t] = i;
@@ -384,19 +316,19 @@ int build_layout(gar_hip_solver *s) {
       }
     }
   }
-  s->nx0 = s->dims5[0];
-  s->nth0 = nth_eff[0];
-  s->n0 = s->nx0 + s->nc0;
+  s.nx0 = s.dims5[0];
+  s.nth0 = nth_eff[0];
+  s.n0 = s.nx0 + s.nc0;
   int64_t in = 0, fo = 0;
-  s->G0_off = in;
-  in += (int64_t)s->nc0 * s->nx0;
-  s->g0_off = in;
-  in += s->nc0;
+  s.G0_off = in;
+  in += (int64_t)s.nc0 * s.nx0;
+  s.g0_off = in;
+  in += s.nc0;
   in = (in + 1) & ~(int64_t)1;
-  int64_t x = 0, u = 0, v = 0, l = s->nc0;
+  int64_t x = 0, u = 0, v = 0, l = s.nc0;
   for (int t = 0; t <= N; ++t) {
-    const int32_t *d = &s->dims5[5 * t];
-    gar_stage_meta &m = s->meta[t];
+    const int32_t *d = &s.dims5[5 * t];
+    gar_stage_meta &m = s.meta[t];
     m.nx = d[0]; m.nu = d[1]; m.nc = d[2]; m.nx2 = d[3];
     m.nth = nth_eff[t];
     m.flags = flags[t];
@@ -405,73 +337,77 @@ int build_layout(gar_hip_solver *s) {
     in += gar_knot_doubles(d[0], d[1], d[2], d[3], (flags[t] & GAR_KNOT_HAS_PARAM) ? d[4] : 0);
     in = (in + 1) & ~(int64_t)1; // keep records 16-byte aligned
     m.fac_off = fo;
-    fo += gar_factor_doubles(d[0], d[1], d[2], s->dense ? 2 * d[3] : d[3], nth_eff[t]);
+    fo += gar_factor_doubles(d[0], d[1], d[2], s.dense ? 2 * d[3] : d[3], nth_eff[t]);
     fo = (fo + 1) & ~(int64_t)1;
     m.x_off = (int32_t)x; x += d[0];
     m.u_off = (int32_t)u; u += d[1];
     m.v_off = (int32_t)v; v += d[2];
     m.l_off = (int32_t)(t == 0 ? 0 : l);
     if (t > 0)
-      l += s->dims5[5 * (t - 1) + 3];
+      l += s.dims5[5 * (t - 1) + 3];
   }
   // lbdas[t] (t>=1) has nx2 of stage t-1: recompute l offsets cleanly
   {
-    int64_t lo = s->nc0;
-    s->meta[0].l_off = 0;
+    int64_t lo = s.nc0;
+    s.meta[0].l_off = 0;
     for (int t = 1; t <= N; ++t) {
-      s->meta[t].l_off = (int32_t)lo;
-      lo += s->dims5[5 * (t - 1) + 3];
+      s.meta[t].l_off = (int32_t)lo;
+      lo += s.dims5[5 * (t - 1) + 3];
     }
     l = lo;
   }
-  s->prob_doubles = in;
-  s->fac_doubles = fo;
-  s->sol_x = 0;
-  s->sol_u = x;
-  s->sol_v = x + u;
-  s->sol_l = x + u + v;
+  s.prob_doubles = in;
+  s.fac_doubles = fo;
+  s.sol_x = 0;
+  s.sol_u = x;
+  s.sol_v = x + u;
+  s.sol_l = x + u + v;
   for (int t = 0; t <= N; ++t) {
-    s->meta[t].u_off += (int32_t)s->sol_u;
-    s->meta[t].v_off += (int32_t)s->sol_v;
-    s->meta[t].l_off += (int32_t)s->sol_l;
+    s.meta[t].u_off += (int32_t)s.sol_u;
+    s.meta[t].v_off += (int32_t)s.sol_v;
+    s.meta[t].l_off += (int32_t)s.sol_l;
   }
-  s->sol_doubles = (x + u + v + l + 1) & ~(int64_t)1;
+  s.sol_doubles = (x + u + v + l + 1) & ~(int64_t)1;
   { // derivative buffer: header G0 | g0 | init Hxx, then one record per stage (even offsets)
     long long p = 0;
-    s->d_G0 = p; p += (long long)s->nc0 * s->nx0;
-    s->d_g0 = p; p += s->nc0;
-    s->d_iH = p; p += (long long)s->nx0 * s->nx0;
+    s.d_G0 = p; p += (long long)s.nc0 * s.nx0;
+    s.d_g0 = p; p += s.nc0;
+    s.d_iH = p; p += (long long)s.nx0 * s.nx0;
     p = (p + 1) & ~1ll;
-    s->deriv_off.assign(N + 1, 0);
+    s.deriv_off.assign(N + 1, 0);
     for (int t = 0; t <= N; ++t) {
-      const int32_t *d = &s->dims5[5 * t];
-      s->deriv_off[t] = p;
+      const int32_t *d = &s.dims5[5 * t];
+      s.deriv_off[t] = p;
       p += gar_deriv_layout(d[0], d[1], d[2], d[3]).total;
       p = (p + 1) & ~1ll;
     }
-    s->deriv_doubles = p;
+    s.deriv_doubles = p;
   }
   {
     long long pf = 0, pb = 0;
-    s->gain_off.assign(2 * (size_t)(N + 1), 0);
+    s.gain_off.assign(2 * (size_t)(N + 1), 0);
     for (int t = 0; t <= N; ++t) {
-      const int32_t *d = &s->dims5[5 * t];
-      const long long nr = (long long)d[1] + d[2] + (s->dense ? 2 * d[3] : d[3]);
-      s->gain_off[2 * t] = pf;
-      s->gain_off[2 * t + 1] = pb;
+      const int32_t *d = &s.dims5[5 * t];
+      const long long nr = (long long)d[1] + d[2] + (s.dense ? 2 * d[3] : d[3]);
+      s.gain_off[2 * t] = pf;
+      s.gain_off[2 * t + 1] = pb;
       pf += nr;
       pb += nr * d[0];
     }
-    s->ff_all_doubles = pf;
-    s->fb_all_doubles = pb;
+    s.ff_all_doubles = pf;
+    s.fb_all_doubles = pb;
   }
-  s->init_doubles = ((int64_t)s->n0 + (int64_t)s->n0 * s->nth0 + s->nth0 +
-                     (int64_t)s->nth0 * s->nth0 + 1) & ~(int64_t)1;
-  s->ring0 = 0;
-  s->uni_in0 = s->meta[0].in_off;
-  s->uni_in_rec = N > 1 ? s->meta[1].in_off - s->meta[0].in_off : s->meta[N].in_off - s->meta[0].in_off;
-  s->uni_fac_rec = N > 1 ? s->meta[1].fac_off - s->meta[0].fac_off : s->meta[N].fac_off;
+  s.init_doubles = ((int64_t)s.n0 + (int64_t)s.n0 * s.nth0 + s.nth0 + (int64_t)s.nth0 * s.nth0 + 1) & ~(int64_t)1;
+  s.ring0 = 0;
+  s.uni_in0 = s.meta[0].in_off;
+  s.uni_in_rec = N > 1 ? s.meta[1].in_off - s.meta[0].in_off : s.meta[N].in_off - s.meta[0].in_off;
+  s.uni_fac_rec = N > 1 ? s.meta[1].fac_off - s.meta[0].fac_off : s.meta[N].fac_off;
   return GAR_HIP_OK;
+}
+
+// the layout of the caller-facing records: the solver's own unless it is padded
+inline const gar::HostLayout &caller_layout(const gar_hip_solver *s) {
+  return s->ulay ? *s->ulay : static_cast<const gar::HostLayout &>(*s);
 }
 
 int plan_lds(gar_hip_solver *s) {
@@ -771,6 +707,9 @@ int write_block(gar_hip_solver *s, int b, int64_t off, const double *src, int64_
   return GAR_HIP_OK;
 }
 
+// the condensed solve's info slots (residual, steps, scale, resolved) in a problem's scratch: behind its blocks
+inline int64_t cond_info_off(const gar_hip_solver *s) { return 4 * (int64_t)(2 * s->num_legs) * ((int64_t)s->nxb * s->nxb + s->nxb); }
+
 gar::LegParams make_leg_params(gar_hip_solver *s) {
   gar::LegParams Q{};
   const int N = s->horizon;
@@ -788,14 +727,14 @@ gar::LegParams make_leg_params(gar_hip_solver *s) {
   Q.meta = s->d_meta;
   Q.skip = nullptr;
   if (s->fold) { // the wave-leg family sweeps the folded knots and keeps its own (nc = 0) factor records
-    const gar_hip_solver *f = s->flay;
+    const gar::HostLayout &f = *s->flay;
     Q.M.prob = s->d_prob2;
     Q.M.fac = s->d_fac2;
-    Q.M.prob_stride = f->prob_doubles;
-    Q.M.fac_stride = f->fac_doubles;
-    Q.M.in_off0 = f->uni_in0;
-    Q.M.in_rec = f->uni_in_rec;
-    Q.M.in_offN = f->meta[N].in_off;
+    Q.M.prob_stride = f.prob_doubles;
+    Q.M.fac_stride = f.fac_doubles;
+    Q.M.in_off0 = f.uni_in0;
+    Q.M.in_rec = f.uni_in_rec;
+    Q.M.in_offN = f.meta[N].in_off;
     Q.meta = s->d_meta2;
     Q.skip = s->d_status + s->batch + 4; // problems with D != 0: the generic leg kernels take them
   }
@@ -810,11 +749,8 @@ gar::LegParams make_leg_params(gar_hip_solver *s) {
   Q.boundary = s->d_bound_local;
   Q.boundary_stride = (long long)s->legs_per_rank * s->tuple_doubles;
   Q.tuple_doubles = (int)s->tuple_doubles;
-  {
-    const int64_t nblk = 2 * s->num_legs, bs = (int64_t)s->nxb * s->nxb;
-    Q.cinfo = s->d_cscratch ? s->d_cscratch + 4 * nblk * bs + 4 * nblk * s->nxb : nullptr;
-    Q.cinfo_stride = s->cscratch_doubles;
-  }
+  Q.cinfo = s->d_cscratch ? s->d_cscratch + cond_info_off(s) : nullptr;
+  Q.cinfo_stride = s->cscratch_doubles;
   return Q;
 }
 
@@ -828,7 +764,7 @@ size_t fold_lds_bytes(const gar_hip_solver *s) {
 }
 gar::FoldParams make_fold_params(gar_hip_solver *s) {
   gar::FoldParams F{};
-  const gar_hip_solver *f = s->flay;
+  const gar::HostLayout &f = *s->flay;
   F.meta = s->d_meta;
   F.meta2 = s->d_meta2;
   F.prob = s->d_prob;
@@ -837,9 +773,9 @@ gar::FoldParams make_fold_params(gar_hip_solver *s) {
   F.fac2 = s->d_fac2;
   F.sol = s->d_sol;
   F.prob_stride = s->prob_doubles;
-  F.prob2_stride = f->prob_doubles;
+  F.prob2_stride = f.prob_doubles;
   F.fac_stride = s->fac_doubles;
-  F.fac2_stride = f->fac_doubles;
+  F.fac2_stride = f.fac_doubles;
   F.sol_stride = s->sol_doubles;
   F.coupled = s->d_status + s->batch + 4;
   F.horizon = s->horizon;
@@ -928,29 +864,32 @@ void free_device(gar_hip_solver *s) {
   s->h_prob = nullptr;
 }
 
+// the two idioms of allocate(): a zeroed device buffer; a kernel's opt-in to `doubles` of dynamic LDS (> 64 KiB needs it)
+template <class T> hipError_t dev_zalloc(T **p, size_t bytes) {
+  const hipError_t e = gar_dev_malloc((void **)p, bytes);
+  return e != hipSuccess ? e : hipMemset(*p, 0, bytes);
+}
+template <class K> hipError_t max_lds(K kernel, size_t doubles) {
+  return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(doubles * sizeof(double)));
+}
+
 int allocate(gar_hip_solver *s) {
   const size_t B = (size_t)s->batch;
   HIP_TRY(gar_dev_malloc((void **)&s->d_meta, sizeof(gar_stage_meta) * s->meta.size()));
   HIP_TRY(hipMemcpy(s->d_meta, s->meta.data(), sizeof(gar_stage_meta) * s->meta.size(),
                     hipMemcpyHostToDevice));
-  HIP_TRY(gar_dev_malloc((void **)&s->d_prob, sizeof(double) * (size_t)s->prob_doubles * B));
-  HIP_TRY(hipMemset(s->d_prob, 0, sizeof(double) * (size_t)s->prob_doubles * B));
-  HIP_TRY(gar_dev_malloc((void **)&s->d_fac, sizeof(double) * (size_t)s->fac_doubles * B));
-  HIP_TRY(hipMemset(s->d_fac, 0, sizeof(double) * (size_t)s->fac_doubles * B));
-  HIP_TRY(gar_dev_malloc((void **)&s->d_sol, sizeof(double) * (size_t)s->sol_doubles * B));
-  HIP_TRY(hipMemset(s->d_sol, 0, sizeof(double) * (size_t)s->sol_doubles * B));
-  HIP_TRY(gar_dev_malloc((void **)&s->d_init, sizeof(double) * (size_t)s->init_doubles * B));
-  HIP_TRY(hipMemset(s->d_init, 0, sizeof(double) * (size_t)s->init_doubles * B));
+  HIP_TRY(dev_zalloc(&s->d_prob, sizeof(double) * (size_t)s->prob_doubles * B));
+  HIP_TRY(dev_zalloc(&s->d_fac, sizeof(double) * (size_t)s->fac_doubles * B));
+  HIP_TRY(dev_zalloc(&s->d_sol, sizeof(double) * (size_t)s->sol_doubles * B));
+  HIP_TRY(dev_zalloc(&s->d_init, sizeof(double) * (size_t)s->init_doubles * B));
   HIP_TRY(gar_dev_malloc((void **)&s->d_theta, sizeof(double) * (size_t)std::max(s->nth0, 1) * B));
   // per-problem failure flags, then the four slow-path counters (MfmaParams::slow), then MfmaParams::resume
-  HIP_TRY(gar_dev_malloc((void **)&s->d_status, sizeof(int) * (2 * B + 4)));
-  HIP_TRY(hipMemset(s->d_status, 0, sizeof(int) * (2 * B + 4)));
+  HIP_TRY(dev_zalloc(&s->d_status, sizeof(int) * (2 * B + 4)));
   if (s->num_legs > 1) {
     const int chunk = s->legs_per_rank; // >= this rank's own leg count; equal-sized chunks for the all-gather
     const int nblk = 2 * s->num_legs;
     const size_t bs = (size_t)s->nxb * s->nxb;
-    HIP_TRY(gar_dev_malloc((void **)&s->d_bound_local, sizeof(double) * s->tuple_doubles * chunk * B));
-    HIP_TRY(hipMemset(s->d_bound_local, 0, sizeof(double) * s->tuple_doubles * chunk * B));
+    HIP_TRY(dev_zalloc(&s->d_bound_local, sizeof(double) * s->tuple_doubles * chunk * B));
     if (s->world == 1) {
       s->d_bound_all = s->d_bound_local;
       s->bound_all_owned = false;
@@ -960,11 +899,10 @@ int allocate(gar_hip_solver *s) {
       s->bound_all_owned = true;
     }
     HIP_TRY(gar_dev_malloc((void **)&s->d_csol, sizeof(double) * (size_t)nblk * s->nxb * B));
-    s->cscratch_doubles = (int64_t)(4 * nblk * bs + 4 * (size_t)nblk * s->nxb + 4);
-    HIP_TRY(gar_dev_malloc((void **)&s->d_cscratch, sizeof(double) * (size_t)s->cscratch_doubles * B));
+    s->cscratch_doubles = cond_info_off(s) + 4;
     // (the info slots behind the blocks -- residual, steps, scale, resolved -- are read by the gar_hip_condensed_*
     // getters: defined before the first solve)
-    HIP_TRY(hipMemset(s->d_cscratch, 0, sizeof(double) * (size_t)s->cscratch_doubles * B));
+    HIP_TRY(dev_zalloc(&s->d_cscratch, sizeof(double) * (size_t)s->cscratch_doubles * B));
     s->cond_lds_doubles = (int)(3 * bs + 4 * s->nxb + 2 + (s->nxb + 16) / 2 + 2 + (s->nxb < 9 ? 9 * s->nxb : 0));
     {
       const char *cr = gar_option("GAR_HIP_CONDENSED_REDUCED");
@@ -978,39 +916,29 @@ int allocate(gar_hip_solver *s) {
     }
   }
   if (s->seg_bwd_kernel) {
-    const gar_hip_solver *f = s->flay;
-    HIP_TRY(gar_dev_malloc((void **)&s->d_fac2, sizeof(double) * (size_t)f->fac_doubles * B));
-    HIP_TRY(hipMemset(s->d_fac2, 0, sizeof(double) * (size_t)f->fac_doubles * B));
-    HIP_TRY(gar_dev_malloc((void **)&s->d_meta2, sizeof(gar_stage_meta) * f->meta.size()));
-    HIP_TRY(hipMemcpy(s->d_meta2, f->meta.data(), sizeof(gar_stage_meta) * f->meta.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipFuncSetAttribute((const void *)s->seg_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(s->seg_lds_doubles * sizeof(double))));
-    HIP_TRY(hipFuncSetAttribute((const void *)gar::gar_leg_param_chain, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(gar::leg_chain_lds_doubles(s->dims5[0]) * sizeof(double))));
-    HIP_TRY(hipFuncSetAttribute((const void *)gar::gar_leg_param_stage, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(gar::leg_stage_lds_doubles(s->dims5[0], s->dims5[1]) * sizeof(double))));
+    const gar::HostLayout &f = *s->flay;
+    HIP_TRY(dev_zalloc(&s->d_fac2, sizeof(double) * (size_t)f.fac_doubles * B));
+    HIP_TRY(gar_dev_malloc((void **)&s->d_meta2, sizeof(gar_stage_meta) * f.meta.size()));
+    HIP_TRY(hipMemcpy(s->d_meta2, f.meta.data(), sizeof(gar_stage_meta) * f.meta.size(), hipMemcpyHostToDevice));
+    HIP_TRY(max_lds(s->seg_bwd_kernel, s->seg_lds_doubles));
+    HIP_TRY(max_lds(gar::gar_leg_param_chain, gar::leg_chain_lds_doubles(s->dims5[0])));
+    HIP_TRY(max_lds(gar::gar_leg_param_stage, gar::leg_stage_lds_doubles(s->dims5[0], s->dims5[1])));
   }
   if (s->fold) {
-    const gar_hip_solver *f = s->flay;
-    HIP_TRY(gar_dev_malloc((void **)&s->d_prob2, sizeof(double) * (size_t)f->prob_doubles * B));
-    HIP_TRY(hipMemset(s->d_prob2, 0, sizeof(double) * (size_t)f->prob_doubles * B));
-    HIP_TRY(gar_dev_malloc((void **)&s->d_fac2, sizeof(double) * (size_t)f->fac_doubles * B));
-    HIP_TRY(hipMemset(s->d_fac2, 0, sizeof(double) * (size_t)f->fac_doubles * B));
-    HIP_TRY(gar_dev_malloc((void **)&s->d_meta2, sizeof(gar_stage_meta) * f->meta.size()));
-    HIP_TRY(hipMemcpy(s->d_meta2, f->meta.data(), sizeof(gar_stage_meta) * f->meta.size(), hipMemcpyHostToDevice));
+    const gar::HostLayout &f = *s->flay;
+    HIP_TRY(dev_zalloc(&s->d_prob2, sizeof(double) * (size_t)f.prob_doubles * B));
+    HIP_TRY(dev_zalloc(&s->d_fac2, sizeof(double) * (size_t)f.fac_doubles * B));
+    HIP_TRY(gar_dev_malloc((void **)&s->d_meta2, sizeof(gar_stage_meta) * f.meta.size()));
+    HIP_TRY(hipMemcpy(s->d_meta2, f.meta.data(), sizeof(gar_stage_meta) * f.meta.size(), hipMemcpyHostToDevice));
     if (s->cseg_on) {
       const size_t units = B * (size_t)s->legs_per_rank;
       HIP_TRY(gar_dev_malloc((void **)&s->d_cseg_resume, sizeof(int) * units));
       HIP_TRY(hipMemset(s->d_cseg_resume, 0xff, sizeof(int) * units));
       for (auto k : s->cseg.backward)
-        HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(s->cseg.backward_lds_doubles * sizeof(double))));
-      HIP_TRY(hipFuncSetAttribute((const void *)s->cseg.leg_end, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(s->cseg.leg_end_lds_doubles * sizeof(double))));
-      HIP_TRY(hipFuncSetAttribute((const void *)s->cseg.chain, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(s->cseg.chain_lds_doubles * sizeof(double))));
-      HIP_TRY(hipFuncSetAttribute((const void *)s->cseg.stage, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(s->cseg.stage_lds_doubles * sizeof(double))));
+        HIP_TRY(max_lds(k, s->cseg.backward_lds_doubles));
+      HIP_TRY(max_lds(s->cseg.leg_end, s->cseg.leg_end_lds_doubles));
+      HIP_TRY(max_lds(s->cseg.chain, s->cseg.chain_lds_doubles));
+      HIP_TRY(max_lds(s->cseg.stage, s->cseg.stage_lds_doubles));
     }
   }
   s->fold_expanded = s->coupled_known = false;
@@ -1025,73 +953,41 @@ int allocate(gar_hip_solver *s) {
   s->dirty_iv.assign(B, {});
   s->dirty = false;
   if (s->dense) {
-    HIP_TRY(hipFuncSetAttribute((const void *)gar::gar_backward_dense,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(s->dense_lds.total * sizeof(double))));
+    HIP_TRY(max_lds(gar::gar_backward_dense, s->dense_lds.total));
     return GAR_HIP_OK;
   }
   if (s->mfma_kernel)
-    HIP_TRY(hipFuncSetAttribute((const void *)s->mfma_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(s->mfma_lds_doubles * sizeof(double))));
+    HIP_TRY(max_lds(s->mfma_kernel, s->mfma_lds_doubles));
   if (s->cyc_setup_kernel) {
-    const int lds = (int)(s->cyc_lds_doubles * sizeof(double));
-    HIP_TRY(hipFuncSetAttribute((const void *)s->cyc_setup_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                lds + (int)(s->cyc_block_doubles * sizeof(double))));
-    HIP_TRY(hipFuncSetAttribute((const void *)s->cyc_reduce_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                2 * lds + 512 + (int)(s->cyc_block_doubles * sizeof(double))));
-    HIP_TRY(hipFuncSetAttribute((const void *)s->cyc_top_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    HIP_TRY(max_lds(s->cyc_setup_kernel, s->cyc_lds_doubles + s->cyc_block_doubles));
+    HIP_TRY(max_lds(s->cyc_reduce_kernel, 2 * s->cyc_lds_doubles + 64 + s->cyc_block_doubles)); // (launch_condensed)
+    HIP_TRY(max_lds(s->cyc_top_kernel, s->cyc_lds_doubles));
   }
   if (s->cond_wave_kernel)
-    HIP_TRY(hipFuncSetAttribute((const void *)s->cond_wave_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(s->cond_wave_lds_doubles * sizeof(double))));
+    HIP_TRY(max_lds(s->cond_wave_kernel, s->cond_wave_lds_doubles));
   if (s->leg_bwd_kernel)
-    HIP_TRY(hipFuncSetAttribute((const void *)s->leg_bwd_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(s->leg_lds_doubles * sizeof(double))));
+    HIP_TRY(max_lds(s->leg_bwd_kernel, s->leg_lds_doubles));
   if (s->wave_kernel)
-    HIP_TRY(hipFuncSetAttribute((const void *)s->wave_kernel,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(s->wave_lds_doubles * s->waves_per_block * sizeof(double))));
+    HIP_TRY(max_lds(s->wave_kernel, s->wave_lds_doubles * s->waves_per_block));
   for (auto k : {s->wave_coupled_kernel, s->wave_bk_kernel})
     if (k)
-      HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(s->wave_lds_doubles * s->waves_per_block * sizeof(double))));
+      HIP_TRY(max_lds(k, s->wave_lds_doubles * s->waves_per_block));
   if (s->lds_error.empty())
-    HIP_TRY(hipFuncSetAttribute((const void *)gar::gar_initial_generic,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(s->lds.total * sizeof(double))));
+    HIP_TRY(max_lds(gar::gar_initial_generic, s->lds.total));
   if (s->n0 <= 128)
-    HIP_TRY(hipFuncSetAttribute(
-        (const void *)gar::gar_initial_wave, hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)(gar::gar_initial_wave_lds_doubles(s->n0, s->nth0) * sizeof(double))));
+    HIP_TRY(max_lds(gar::gar_initial_wave, gar::gar_initial_wave_lds_doubles(s->n0, s->nth0)));
   // > 64 KiB of dynamic LDS needs the opt-in attribute
   if (s->lds_error.empty())
-    HIP_TRY(hipFuncSetAttribute((const void *)gar::gar_backward_generic,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(s->lds.total * sizeof(double))));
+    HIP_TRY(max_lds(gar::gar_backward_generic, s->lds.total));
   if (s->num_legs > 1)
-    HIP_TRY(hipFuncSetAttribute((const void *)gar::gar_condensed_generic,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(s->cond_lds_doubles * sizeof(double))));
+    HIP_TRY(max_lds(gar::gar_condensed_generic, s->cond_lds_doubles));
   if (s->num_legs > 1 && s->cond_reduced)
-    HIP_TRY(hipFuncSetAttribute((const void *)gar::gar_condensed_leg_eliminate,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(gar::gar_condensed_leg_lds_doubles(s->nxb) * sizeof(double))));
+    HIP_TRY(max_lds(gar::gar_condensed_leg_eliminate, gar::gar_condensed_leg_lds_doubles(s->nxb)));
   if (s->num_legs > 1 && s->cond_cr) {
-    HIP_TRY(hipFuncSetAttribute((const void *)gar::gar_condensed_cr_eliminate,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(gar::gar_condensed_leg_lds_doubles(s->nxb) * sizeof(double))));
-    HIP_TRY(hipFuncSetAttribute((const void *)gar::gar_condensed_cr_update, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)std::min<size_t>(160 * 1024, (size_t)gar::gar_condensed_cr_update_lds_doubles(s->nxb, 1) *
-                                                                      sizeof(double))));
-    HIP_TRY(hipFuncSetAttribute((const void *)gar::gar_condensed_cr_assemble, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)((size_t)s->nxb * s->nxb * sizeof(double))));
-    HIP_TRY(hipFuncSetAttribute((const void *)gar::gar_condensed_cr_back, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(gar::gar_condensed_cr_back_lds_doubles(s->nxb, s->num_legs) * sizeof(double))));
+    HIP_TRY(max_lds(gar::gar_condensed_cr_eliminate, gar::gar_condensed_leg_lds_doubles(s->nxb)));
+    HIP_TRY(max_lds(gar::gar_condensed_cr_update, std::min(160 * 1024 / 8, gar::gar_condensed_cr_update_lds_doubles(s->nxb, 1))));
+    HIP_TRY(max_lds(gar::gar_condensed_cr_assemble, s->nxb * s->nxb));
+    HIP_TRY(max_lds(gar::gar_condensed_cr_back, gar::gar_condensed_cr_back_lds_doubles(s->nxb, s->num_legs)));
   }
   return GAR_HIP_OK;
 }
@@ -1144,8 +1040,8 @@ void strip_solution(const gar_hip_solver *s, const double *rec, double *xs, doub
 }
 // one device solution record -> the caller's record layout (ulay)
 void strip_solution_rec(const gar_hip_solver *s, const double *dev, double *rec) {
-  const gar_hip_solver *u = s->ulay;
-  strip_solution(s, dev, rec + u->sol_x, rec + u->sol_u, rec + u->sol_v, rec + u->sol_l);
+  const gar::HostLayout &u = *s->ulay;
+  strip_solution(s, dev, rec + u.sol_x, rec + u.sol_u, rec + u.sol_v, rec + u.sol_l);
 }
 } // namespace
 
@@ -1303,36 +1199,29 @@ gar_hip_solver *create_impl(int device, int horizon, const int32_t *dims5, int n
   s->user_dims5.assign(dims5, dims5 + 5 * (horizon + 1));
   normalise_terminal(s);
   DeviceGuard guard_(device); // the caller's current device is restored on return
+  auto give_up = [s]() -> gar_hip_solver * { // the one way out on failure (g_last_error says why)
+    free_device(s);
+    if (s->own_stream)
+      (void)hipStreamDestroy(s->own_stream);
+    delete s;
+    return nullptr;
+  };
   {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != device) {
       fail(GAR_HIP_ERR_DEVICE, "hipSetDevice failed");
-      delete s;
-      return nullptr;
+      return give_up();
     }
   }
-  if (configure(s) != GAR_HIP_OK) {
-    delete s->ulay;
-    delete s->flay;
-    delete s;
-    return nullptr;
-  }
+  if (configure(s) != GAR_HIP_OK)
+    return give_up();
   if (hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking) != hipSuccess) {
     fail(GAR_HIP_ERR_DEVICE, "hipStreamCreate failed");
-    delete s->ulay;
-    delete s->flay;
-    delete s;
-    return nullptr;
+    return give_up();
   }
   s->stream = s->own_stream;
-  if (allocate(s) != GAR_HIP_OK) {
-    free_device(s);
-    (void)hipStreamDestroy(s->own_stream);
-    delete s->ulay;
-    delete s->flay;
-    delete s;
-    return nullptr;
-  }
+  if (allocate(s) != GAR_HIP_OK)
+    return give_up();
   { // the default schedule is the library's own choice (GAR_HIP_PIPELINE = auto | 0 | 2; gar_hip_set_pipeline overrides)
     const char *pl = gar_option("GAR_HIP_PIPELINE");
     const int want = pl ? (pl[0] == '0' ? 0 : pl[0] == '2' ? 2 : -1) : -1;
@@ -1409,8 +1298,6 @@ void gar_hip_solver_destroy(gar_hip_solver *s) {
     (void)hipEventDestroy(s->ev_status);
     (void)hipEventDestroy(s->ev_sol);
   }
-  delete s->ulay;
-  delete s->flay;
   delete s;
 }
 
@@ -1434,9 +1321,9 @@ int gar_hip_sync(gar_hip_solver *s) {
 }
 
 // (the caller's records: under padding they are laid out by the caller's dimensions, `ulay`)
-int64_t gar_hip_problem_doubles(const gar_hip_solver *s) { return s ? (s->ulay ? s->ulay->prob_doubles : s->prob_doubles) : 0; }
+int64_t gar_hip_problem_doubles(const gar_hip_solver *s) { return s ? caller_layout(s).prob_doubles : 0; }
 int64_t gar_hip_factors_doubles(const gar_hip_solver *s) { return s ? s->fac_doubles : 0; }
-int64_t gar_hip_solution_doubles(const gar_hip_solver *s) { return s ? (s->ulay ? s->ulay->sol_doubles : s->sol_doubles) : 0; }
+int64_t gar_hip_solution_doubles(const gar_hip_solver *s) { return s ? caller_layout(s).sol_doubles : 0; }
 int gar_hip_batch(const gar_hip_solver *s) { return s ? s->batch : 0; }
 int gar_hip_horizon(const gar_hip_solver *s) { return s ? s->horizon : -1; }
 const char *gar_hip_kernel_name(const gar_hip_solver *s) {
@@ -1468,7 +1355,7 @@ const char *gar_hip_condensed_solver_name(const gar_hip_solver *s) {
 int gar_hip_stage_offsets(const gar_hip_solver *s, int t, int64_t out[6]) {
   if (int rc = check_bt(s, 0, t))
     return rc;
-  const gar_stage_meta &m = s->ulay ? s->ulay->meta[t] : s->meta[t];
+  const gar_stage_meta &m = caller_layout(s).meta[t];
   out[0] = m.in_off;
   out[1] = s->meta[t].fac_off; // factor records exist on the device only
   out[2] = m.x_off;
@@ -1481,8 +1368,8 @@ int gar_hip_stage_offsets(const gar_hip_solver *s, int t, int64_t out[6]) {
 int gar_hip_init_offsets(const gar_hip_solver *s, int64_t out[2]) {
   if (!s)
     return fail(GAR_HIP_ERR_ARG, "null solver");
-  out[0] = s->ulay ? s->ulay->G0_off : s->G0_off;
-  out[1] = s->ulay ? s->ulay->g0_off : s->g0_off;
+  out[0] = caller_layout(s).G0_off;
+  out[1] = caller_layout(s).g0_off;
   return GAR_HIP_OK;
 }
 
@@ -1570,12 +1457,12 @@ int gar_hip_upload_packed(gar_hip_solver *s, int b0, int nb, const double *packe
   if (!s || !packed || b0 < 0 || nb < 0 || b0 + nb > s->batch)
     return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_packed: bad argument");
   if (s->padded || s->qr_packed) { // the caller's records: knot by knot through the padding / packing path
-    const gar_hip_solver *u = s->ulay ? s->ulay : s;
+    const gar::HostLayout &u = caller_layout(s);
     for (int b = b0; b < b0 + nb; ++b) {
-      const double *rec = packed + (int64_t)(b - b0) * u->prob_doubles;
+      const double *rec = packed + (int64_t)(b - b0) * u.prob_doubles;
       for (int t = 0; t <= s->horizon; ++t) {
         // (a padded solver is unconstrained and unparameterised; one that only packs Q / R may carry both)
-        const gar_stage_meta &m = u->meta[t];
+        const gar_stage_meta &m = u.meta[t];
         const int nth_st = (m.flags & GAR_KNOT_HAS_PARAM) ? m.nth : 0;
         const gar_knot_offsets o = gar_knot_layout(m.nx, m.nu, m.nc, m.nx2, nth_st);
         const double *k = rec + m.in_off;
@@ -1583,7 +1470,7 @@ int gar_hip_upload_packed(gar_hip_solver *s, int b0, int nb, const double *packe
                                           k + o.C, k + o.D, k + o.d, k + o.Gth, k + o.Gx, k + o.Gu, k + o.Gv, k + o.gamma))
           return rc;
       }
-      if (int rc = gar_hip_set_init(s, b, rec + u->G0_off, rec + u->g0_off))
+      if (int rc = gar_hip_set_init(s, b, rec + u.G0_off, rec + u.g0_off))
         return rc;
     }
     return GAR_HIP_OK;
@@ -1889,8 +1776,8 @@ int gar_hip_backward_blocks(gar_hip_solver *s, const double *const *blocks, cons
   if (int rc = launch_forward(s, nullptr))
     return rc;
   {
-    const gar_hip_solver *u = s->ulay ? s->ulay : s;
-    const size_t nsol = (size_t)u->sol_doubles, ngain = (size_t)(u->ff_all_doubles + u->fb_all_doubles);
+    const gar::HostLayout &u = caller_layout(s);
+    const size_t nsol = (size_t)u.sol_doubles, ngain = (size_t)(u.ff_all_doubles + u.fb_all_doubles);
     // by a kernel's own stores into the pinned buffer: the copy engine is busy with the gains (3.7 / 9.4 MB) and a
     // hipMemcpyAsync would queue behind them (measured: profiles/r04_seam_eager_rollout_ab.json)
     double *dst = s->h_results + (s->padded ? nsol + ngain : 0);
@@ -2031,9 +1918,7 @@ int gar_hip_condensed_info(gar_hip_solver *s, int b, double out[2]) {
   GAR_MULTI(s, gar_hip_condensed_info(s->multi->subs[0], b, out)); // (solved redundantly on every device)
   if (s->num_legs < 2 || !out)
     return fail(GAR_HIP_ERR_ARG, "condensed info needs leg mode");
-  const int64_t nblk = 2 * s->num_legs, bs = (int64_t)s->nxb * s->nxb;
-  const double *info = s->d_cscratch + (int64_t)b * s->cscratch_doubles + 4 * nblk * bs +
-                       4 * nblk * s->nxb;
+  const double *info = s->d_cscratch + (int64_t)b * s->cscratch_doubles + cond_info_off(s);
   if (int rc = d2h(s, out, info, 2))
     return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -2104,15 +1989,15 @@ static int get_gains_dev(gar_hip_solver *s, int b, int t, double *ff, double *fb
 int gar_hip_gains_doubles(const gar_hip_solver *s, int64_t out[2]) {
   if (!s || !out)
     return fail(GAR_HIP_ERR_ARG, "bad argument");
-  out[0] = s->ulay ? s->ulay->ff_all_doubles : s->ff_all_doubles;
-  out[1] = s->ulay ? s->ulay->fb_all_doubles : s->fb_all_doubles;
+  out[0] = caller_layout(s).ff_all_doubles;
+  out[1] = caller_layout(s).fb_all_doubles;
   return GAR_HIP_OK;
 }
 
 int gar_hip_gains_offsets(const gar_hip_solver *s, int t, int64_t out[2]) {
   if (int rc = check_bt(s, 0, t))
     return rc;
-  const std::vector<long long> &go = s->ulay ? s->ulay->gain_off : s->gain_off;
+  const std::vector<long long> &go = caller_layout(s).gain_off;
   out[0] = go[2 * (size_t)t];
   out[1] = go[2 * (size_t)t + 1];
   return GAR_HIP_OK;
@@ -2126,8 +2011,8 @@ static int fetch_results_impl(gar_hip_solver *s, int b, int what, int t_lo, int 
     return rc;
   // the caller's records (under padding: the real rows / columns only); the device solution record is staged
   // behind them when it has to be stripped on the host
-  const gar_hip_solver *u = s->ulay ? s->ulay : s;
-  const size_t nsol = (size_t)u->sol_doubles, ngain = (size_t)(u->ff_all_doubles + u->fb_all_doubles);
+  const gar::HostLayout &u = caller_layout(s);
+  const size_t nsol = (size_t)u.sol_doubles, ngain = (size_t)(u.ff_all_doubles + u.fb_all_doubles);
   const size_t nscratch = s->padded ? (size_t)s->sol_doubles : 0;
   if (!s->h_results) { // first use: the buffers live as long as the solver's layout
     // all three or none: a partial failure must not leave h_results set with the device buffers missing
@@ -2137,9 +2022,9 @@ static int fetch_results_impl(gar_hip_solver *s, int b, int what, int t_lo, int 
     if (e == hipSuccess)
       e = gar_dev_malloc((void **)&dg, sizeof(double) * std::max<size_t>(ngain, 1));
     if (e == hipSuccess)
-      e = gar_dev_malloc((void **)&dgo, sizeof(long long) * u->gain_off.size());
+      e = gar_dev_malloc((void **)&dgo, sizeof(long long) * u.gain_off.size());
     if (e == hipSuccess)
-      e = hipMemcpyAsync(dgo, u->gain_off.data(), sizeof(long long) * u->gain_off.size(), hipMemcpyHostToDevice,
+      e = hipMemcpyAsync(dgo, u.gain_off.data(), sizeof(long long) * u.gain_off.size(), hipMemcpyHostToDevice,
                          s->stream);
     if (e != hipSuccess) {
       if (h)
@@ -2176,20 +2061,20 @@ static int fetch_results_impl(gar_hip_solver *s, int b, int what, int t_lo, int 
     const bool t2 = records_t2(s, b);
     hipLaunchKernelGGL(gar::gar_gather_gains, dim3((unsigned)(t_hi - t_lo)), dim3(256), 0, s->stream,
                        s->d_meta, s->d_fac + (int64_t)b * s->fac_doubles, s->d_gains,
-                       s->d_gains + u->ff_all_doubles, s->d_gain_off, s->horizon, t2 ? 1 : 0,
+                       s->d_gains + u.ff_all_doubles, s->d_gain_off, s->horizon, t2 ? 1 : 0,
                        s->dense ? 1 : 0, s->padded ? s->unx : 0, s->padded ? s->unu : 0, t_lo);
     HIP_TRY(hipGetLastError());
     double *hg = (gains_base ? gains_base : s->h_results) + nsol;
     if (t_lo == 0 && t_hi == s->horizon + 1) {
       HIP_TRY(hipMemcpyAsync(hg, s->d_gains, sizeof(double) * ngain, hipMemcpyDeviceToHost, s->stream));
     } else { // the two slices of this stage range
-      const std::vector<long long> &go = u->gain_off;
-      const long long f0 = go[2 * (size_t)t_lo], f1 = t_hi <= s->horizon ? go[2 * (size_t)t_hi] : u->ff_all_doubles;
-      const long long b0 = go[2 * (size_t)t_lo + 1], b1 = t_hi <= s->horizon ? go[2 * (size_t)t_hi + 1] : u->fb_all_doubles;
+      const std::vector<long long> &go = u.gain_off;
+      const long long f0 = go[2 * (size_t)t_lo], f1 = t_hi <= s->horizon ? go[2 * (size_t)t_hi] : u.ff_all_doubles;
+      const long long b0 = go[2 * (size_t)t_lo + 1], b1 = t_hi <= s->horizon ? go[2 * (size_t)t_hi + 1] : u.fb_all_doubles;
       if (f1 > f0)
         HIP_TRY(hipMemcpyAsync(hg + f0, s->d_gains + f0, sizeof(double) * (size_t)(f1 - f0), hipMemcpyDeviceToHost, s->stream));
       if (b1 > b0)
-        HIP_TRY(hipMemcpyAsync(hg + u->ff_all_doubles + b0, s->d_gains + u->ff_all_doubles + b0,
+        HIP_TRY(hipMemcpyAsync(hg + u.ff_all_doubles + b0, s->d_gains + u.ff_all_doubles + b0,
                                sizeof(double) * (size_t)(b1 - b0), hipMemcpyDeviceToHost, s->stream));
     }
   }
@@ -2218,12 +2103,12 @@ static int prefetch_impl(gar_hip_solver *s, int b) {
     HIP_TRY(hipEventCreateWithFlags(&s->ev_main, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&s->ev_pref, hipEventDisableTiming));
   }
-  const gar_hip_solver *u = s->ulay ? s->ulay : s;
-  const size_t nsol = (size_t)u->sol_doubles, ngain = (size_t)(u->ff_all_doubles + u->fb_all_doubles);
+  const gar::HostLayout &u = caller_layout(s);
+  const size_t nsol = (size_t)u.sol_doubles, ngain = (size_t)(u.ff_all_doubles + u.fb_all_doubles);
   HIP_TRY(hipEventRecord(s->ev_main, s->stream));
   HIP_TRY(hipStreamWaitEvent(s->aux_stream, s->ev_main, 0));
   hipLaunchKernelGGL(gar::gar_gather_gains, dim3((unsigned)(s->horizon + 1)), dim3(256), 0, s->aux_stream, s->d_meta,
-                     s->d_fac + (int64_t)b * s->fac_doubles, s->d_gains, s->d_gains + u->ff_all_doubles, s->d_gain_off,
+                     s->d_fac + (int64_t)b * s->fac_doubles, s->d_gains, s->d_gains + u.ff_all_doubles, s->d_gain_off,
                      s->horizon, records_t2(s, b) ? 1 : 0, s->dense ? 1 : 0, s->padded ? s->unx : 0,
                      s->padded ? s->unu : 0, 0);
   HIP_TRY(hipGetLastError());
@@ -2257,11 +2142,11 @@ int gar_hip_prefetch_gains(gar_hip_solver *s, int b) {
 const double *gar_hip_host_results(gar_hip_solver *s, int64_t offs[3]) {
   if (!s)
     return nullptr;
-  const gar_hip_solver *u = s->ulay ? s->ulay : s;
+  const gar::HostLayout &u = caller_layout(s);
   if (offs) {
     offs[0] = 0;
-    offs[1] = u->sol_doubles;
-    offs[2] = u->sol_doubles + u->ff_all_doubles;
+    offs[1] = u.sol_doubles;
+    offs[2] = u.sol_doubles + u.ff_all_doubles;
   }
   if (s->multi)
     return s->multi->h_results;
@@ -2271,13 +2156,13 @@ const double *gar_hip_host_results(gar_hip_solver *s, int64_t offs[3]) {
 int gar_hip_get_gains_all(gar_hip_solver *s, int b, double *ff_all, double *fb_all) {
   if (int rc = gar_hip_fetch_results(s, b, 2))
     return rc;
-  const gar_hip_solver *u = s->ulay ? s->ulay : s;
+  const gar::HostLayout &u = caller_layout(s);
   const double *h = gar_hip_host_results(s, nullptr);
   if (ff_all)
-    std::memcpy(ff_all, h + u->sol_doubles, sizeof(double) * (size_t)u->ff_all_doubles);
+    std::memcpy(ff_all, h + u.sol_doubles, sizeof(double) * (size_t)u.ff_all_doubles);
   if (fb_all)
-    std::memcpy(fb_all, h + u->sol_doubles + u->ff_all_doubles,
-                sizeof(double) * (size_t)u->fb_all_doubles);
+    std::memcpy(fb_all, h + u.sol_doubles + u.ff_all_doubles,
+                sizeof(double) * (size_t)u.fb_all_doubles);
   return GAR_HIP_OK;
 }
 
@@ -2384,16 +2269,16 @@ int gar_hip_debug_trace(gar_hip_solver *s, int enable, long long out[64]) {
 }
 
 // (the derivative records speak the CALLER's dimensions: under padding the layout is the caller-facing one, `ulay`)
-int64_t gar_hip_deriv_doubles(const gar_hip_solver *s) { return s ? (s->ulay ? s->ulay->deriv_doubles : s->deriv_doubles) : 0; }
+int64_t gar_hip_deriv_doubles(const gar_hip_solver *s) { return s ? caller_layout(s).deriv_doubles : 0; }
 
 int gar_hip_deriv_offsets(const gar_hip_solver *s, int t, int64_t out[4]) {
   if (int rc = check_bt(s, 0, t))
     return rc;
-  const gar_hip_solver *u = s->ulay ? s->ulay : s;
-  out[0] = u->deriv_off[t];
-  out[1] = u->d_G0;
-  out[2] = u->d_g0;
-  out[3] = u->d_iH;
+  const gar::HostLayout &u = caller_layout(s);
+  out[0] = u.deriv_off[t];
+  out[1] = u.d_G0;
+  out[2] = u.d_g0;
+  out[3] = u.d_iH;
   return GAR_HIP_OK;
 }
 
@@ -2405,24 +2290,24 @@ int gar_hip_update_lq_subproblem_device(gar_hip_solver *s, const double *deriv_d
   GAR_MULTI(s, fail(GAR_HIP_ERR_UNSUPPORTED, "device-resident LQ assembly on a multi-device solver: one derivative buffer per device would be needed"));
   if (int rc = commit(s)) // pending host staging first; later host writes flush only their own ranges
     return rc;
-  const gar_hip_solver *u = s->ulay ? s->ulay : s; // the layout of the derivative buffer: the caller's dimensions
+  const gar::HostLayout &u = caller_layout(s); // the layout of the derivative buffer: the caller's dimensions
   if (!s->d_deriv_off) {
-    HIP_TRY(gar_dev_malloc((void **)&s->d_deriv_off, sizeof(long long) * u->deriv_off.size()));
-    HIP_TRY(hipMemcpy(s->d_deriv_off, u->deriv_off.data(), sizeof(long long) * u->deriv_off.size(),
+    HIP_TRY(gar_dev_malloc((void **)&s->d_deriv_off, sizeof(long long) * u.deriv_off.size()));
+    HIP_TRY(hipMemcpy(s->d_deriv_off, u.deriv_off.data(), sizeof(long long) * u.deriv_off.size(),
                       hipMemcpyHostToDevice));
   }
   gar::UpdateParams U{};
   U.meta = s->d_meta;
   U.deriv = deriv_dev;
   U.prob = s->d_prob;
-  U.deriv_stride = u->deriv_doubles;
+  U.deriv_stride = u.deriv_doubles;
   U.prob_stride = s->prob_doubles;
   U.G0_off = s->G0_off;
   U.g0_off = s->g0_off;
   U.deriv_off = s->d_deriv_off;
-  U.d_G0 = u->d_G0;
-  U.d_g0 = u->d_g0;
-  U.d_iH = u->d_iH;
+  U.d_G0 = u.d_G0;
+  U.d_g0 = u.d_g0;
+  U.d_iH = u.d_iH;
   U.horizon = s->horizon;
   U.nc0 = s->nc0;
   U.nx0 = s->nx0;
@@ -2446,22 +2331,22 @@ int gar_hip_download_packed(gar_hip_solver *s, int b0, int nb, double *packed) {
   if (int rc = commit(s))
     return rc;
   if (s->padded) { // device records -> the caller's: the real rows / columns of every block
-    const gar_hip_solver *u = s->ulay;
+    const gar::HostLayout &u = *s->ulay;
     std::vector<double> dev((size_t)s->prob_doubles);
     for (int b = b0; b < b0 + nb; ++b) {
       HIP_TRY(hipMemcpyAsync(dev.data(), s->d_prob + (int64_t)b * s->prob_doubles, sizeof(double) * dev.size(),
                              hipMemcpyDeviceToHost, s->stream));
       HIP_TRY(hipStreamSynchronize(s->stream));
-      double *rec = packed + (int64_t)(b - b0) * u->prob_doubles;
-      std::memset(rec, 0, sizeof(double) * (size_t)u->prob_doubles);
+      double *rec = packed + (int64_t)(b - b0) * u.prob_doubles;
+      std::memset(rec, 0, sizeof(double) * (size_t)u.prob_doubles);
       auto take = [](double *dst, const double *src, int r, int c, int R) {
         for (int j = 0; j < c; ++j)
           std::memcpy(dst + (size_t)j * r, src + (size_t)j * R, sizeof(double) * (size_t)r);
       };
-      take(rec + u->G0_off, dev.data() + s->G0_off, s->user_nc0, s->unx, s->nc0);
-      take(rec + u->g0_off, dev.data() + s->g0_off, s->user_nc0, 1, s->nc0);
+      take(rec + u.G0_off, dev.data() + s->G0_off, s->user_nc0, s->unx, s->nc0);
+      take(rec + u.g0_off, dev.data() + s->g0_off, s->user_nc0, 1, s->nc0);
       for (int t = 0; t <= s->horizon; ++t) {
-        const gar_stage_meta &m = u->meta[t], &M = s->meta[t];
+        const gar_stage_meta &m = u.meta[t], &M = s->meta[t];
         const gar_knot_offsets o = gar_knot_layout(m.nx, m.nu, 0, m.nx2, 0), O = gar_knot_layout(M.nx, M.nu, 0, M.nx2, 0);
         double *k = rec + m.in_off;
         const double *K = dev.data() + M.in_off;
@@ -2637,11 +2522,7 @@ int gar_hip_cycle_append(gar_hip_solver *s, const int32_t d[5]) {
     trial.world = s->world;
     trial.dense = s->dense;
     trial.user_dims5 = nd;
-    const int rc = configure(&trial);
-    delete trial.ulay;
-    delete trial.flay;
-    trial.ulay = trial.flay = nullptr;
-    if (rc != GAR_HIP_OK)
+    if (int rc = configure(&trial))
       return rc; // g_last_error says why
   }
   HIP_TRY(hipStreamSynchronize(s->stream));

@@ -159,7 +159,7 @@ int launch_backward(gar_hip_solver *s, double mueq, int l0 = -1, int l1 = -1) {
     return GAR_HIP_OK;
   }
   if (s->seg_bwd_kernel) { // segment legs (gar_leg_seg.hpp): plain part, then the parameter recursion + tuples
-    const gar_hip_solver *f = s->flay;
+    const gar::HostLayout &f = *s->flay;
     const int N = s->horizon;
     gar::MfmaParams M{};
     M.prob = s->d_prob;
@@ -168,12 +168,12 @@ int launch_backward(gar_hip_solver *s, double mueq, int l0 = -1, int l1 = -1) {
     M.slow = s->d_status + s->batch;
     M.resume = s->d_status + s->batch + 4;
     M.prob_stride = s->prob_doubles;
-    M.fac_stride = f->fac_doubles;
+    M.fac_stride = f.fac_doubles;
     M.in_off0 = s->uni_in0;
     M.in_rec = s->uni_in_rec;
     M.in_offN = s->meta[N].in_off;
-    M.fac_rec = f->uni_fac_rec;
-    M.fac_offN = f->meta[N].fac_off;
+    M.fac_rec = f.uni_fac_rec;
+    M.fac_offN = f.meta[N].fac_off;
     M.horizon = N;
     M.mueq = mueq;
     {
@@ -195,7 +195,7 @@ int launch_backward(gar_hip_solver *s, double mueq, int l0 = -1, int l1 = -1) {
     Q.status = s->d_status;
     Q.prob_stride = s->prob_doubles;
     Q.fac_stride = s->fac_doubles;
-    Q.fac2_stride = f->fac_doubles;
+    Q.fac2_stride = f.fac_doubles;
     Q.boundary_stride = (long long)s->legs_per_rank * s->tuple_doubles;
     Q.horizon = N;
     Q.num_legs = s->num_legs;

@@ -59,8 +59,6 @@ struct gar_multi {
 
 namespace {
 
-inline const gar_hip_solver *caller_layout(const gar_hip_solver *s) { return s->ulay ? s->ulay : s; }
-
 void multi_ranges(gar_hip_solver *s) {
   gar_multi *M = s->multi;
   const int W = (int)M->subs.size(), J = s->num_legs, N = s->horizon;
@@ -104,8 +102,6 @@ void multi_destroy(gar_hip_solver *s) {
     (void)hipHostFree(M->h_results);
   delete M;
   s->multi = nullptr;
-  delete s->ulay;
-  delete s->flay;
   delete s;
 }
 
@@ -142,11 +138,11 @@ int multi_upload_packed(gar_hip_solver *s, int b0, int nb, const double *packed)
     return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_packed: bad argument");
   const int N = s->horizon;
   if (s->padded) { // the caller's records, knot by knot through the padding path of the stage's owner
-    const gar_hip_solver *u = s->ulay;
+    const gar::HostLayout &u = *s->ulay;
     for (int b = b0; b < b0 + nb; ++b) {
-      const double *rec = packed + (int64_t)(b - b0) * u->prob_doubles;
+      const double *rec = packed + (int64_t)(b - b0) * u.prob_doubles;
       for (int t = 0; t <= N; ++t) {
-        const gar_stage_meta &m = u->meta[t];
+        const gar_stage_meta &m = u.meta[t];
         const gar_knot_offsets o = gar_knot_layout(m.nx, m.nu, 0, m.nx2, 0);
         const double *k = rec + m.in_off;
         if (int rc = gar_hip_upload_stage(M->subs[(size_t)M->owner[(size_t)t]], b, t, k + o.Q, k + o.S, k + o.R, k + o.q,
@@ -154,7 +150,7 @@ int multi_upload_packed(gar_hip_solver *s, int b0, int nb, const double *packed)
                                           nullptr, nullptr, nullptr, nullptr))
           return rc;
       }
-      if (int rc = multi_set_init(s, b, rec + u->G0_off, rec + u->g0_off))
+      if (int rc = multi_set_init(s, b, rec + u.G0_off, rec + u.g0_off))
         return rc;
     }
     return GAR_HIP_OK;
@@ -176,16 +172,16 @@ int multi_download_packed(gar_hip_solver *s, int b0, int nb, double *packed) {
   gar_multi *M = s->multi;
   if (!packed || b0 < 0 || nb < 0 || b0 + nb > s->batch)
     return fail(GAR_HIP_ERR_ARG, "gar_hip_download_packed: bad argument");
-  const gar_hip_solver *L = caller_layout(s);
+  const gar::HostLayout &L = caller_layout(s);
   const int N = s->horizon;
-  std::vector<double> tmp((size_t)L->prob_doubles * (size_t)nb);
+  std::vector<double> tmp((size_t)L.prob_doubles * (size_t)nb);
   for (size_t r = 0; r < M->subs.size(); ++r) {
     if (int rc = gar_hip_download_packed(M->subs[r], b0, nb, tmp.data()))
       return rc;
-    const int64_t lo = r == 0 ? 0 : L->meta[(size_t)M->t_lo[r]].in_off;
-    const int64_t hi = M->t_hi[r] <= N ? L->meta[(size_t)M->t_hi[r]].in_off : L->prob_doubles;
+    const int64_t lo = r == 0 ? 0 : L.meta[(size_t)M->t_lo[r]].in_off;
+    const int64_t hi = M->t_hi[r] <= N ? L.meta[(size_t)M->t_hi[r]].in_off : L.prob_doubles;
     for (int k = 0; k < nb; ++k)
-      std::memcpy(packed + (int64_t)k * L->prob_doubles + lo, tmp.data() + (int64_t)k * L->prob_doubles + lo,
+      std::memcpy(packed + (int64_t)k * L.prob_doubles + lo, tmp.data() + (int64_t)k * L.prob_doubles + lo,
                   sizeof(double) * (size_t)(hi - lo));
   }
   return GAR_HIP_OK;
@@ -300,32 +296,32 @@ int multi_counters(gar_hip_solver *s, int64_t out[2], int (*get)(gar_hip_solver 
 struct SolRange { int64_t x0, x1, u0, u1, v0, v1, l0, l1; };
 SolRange multi_sol_range(const gar_hip_solver *s, size_t r) {
   const gar_multi *M = s->multi;
-  const gar_hip_solver *L = caller_layout(s);
+  const gar::HostLayout &L = caller_layout(s);
   const int N = s->horizon, lo = M->t_lo[r], hi = M->t_hi[r];
   SolRange R;
-  int64_t nl = L->nc0;
+  int64_t nl = L.nc0;
   for (int t = 0; t < N; ++t)
-    nl += L->meta[(size_t)t].nx2;
-  R.x0 = L->meta[(size_t)lo].x_off - L->sol_x;
-  R.x1 = (hi <= N ? L->meta[(size_t)hi].x_off : L->sol_u) - L->sol_x;
-  R.u0 = L->meta[(size_t)lo].u_off - L->sol_u;
-  R.u1 = (hi <= N ? L->meta[(size_t)hi].u_off : L->sol_v) - L->sol_u;
-  R.v0 = L->meta[(size_t)lo].v_off - L->sol_v;
-  R.v1 = (hi <= N ? L->meta[(size_t)hi].v_off : L->sol_l) - L->sol_v;
+    nl += L.meta[(size_t)t].nx2;
+  R.x0 = L.meta[(size_t)lo].x_off - L.sol_x;
+  R.x1 = (hi <= N ? L.meta[(size_t)hi].x_off : L.sol_u) - L.sol_x;
+  R.u0 = L.meta[(size_t)lo].u_off - L.sol_u;
+  R.u1 = (hi <= N ? L.meta[(size_t)hi].u_off : L.sol_v) - L.sol_u;
+  R.v0 = L.meta[(size_t)lo].v_off - L.sol_v;
+  R.v1 = (hi <= N ? L.meta[(size_t)hi].v_off : L.sol_l) - L.sol_v;
   // lbdas[t] travels with stage t: at a leg start it comes from the condensed solution every device holds
   // (parallel-solver.hxx:215-220), otherwise from the leg that holds stage t - 1 -- the same leg
-  R.l0 = lo == 0 ? 0 : L->meta[(size_t)lo].l_off - L->sol_l;
-  R.l1 = hi <= N ? L->meta[(size_t)hi].l_off - L->sol_l : nl;
+  R.l0 = lo == 0 ? 0 : L.meta[(size_t)lo].l_off - L.sol_l;
+  R.l1 = hi <= N ? L.meta[(size_t)hi].l_off - L.sol_l : nl;
   return R;
 }
 
 int multi_get_solution(gar_hip_solver *s, int b, double *xs, double *us, double *vs, double *lbdas) {
   gar_multi *M = s->multi;
-  const gar_hip_solver *L = caller_layout(s);
-  int64_t nl = L->nc0;
+  const gar::HostLayout &L = caller_layout(s);
+  int64_t nl = L.nc0;
   for (int t = 0; t < s->horizon; ++t)
-    nl += L->meta[(size_t)t].nx2;
-  std::vector<double> tx((size_t)(L->sol_u - L->sol_x)), tu((size_t)(L->sol_v - L->sol_u)), tv((size_t)(L->sol_l - L->sol_v)),
+    nl += L.meta[(size_t)t].nx2;
+  std::vector<double> tx((size_t)(L.sol_u - L.sol_x)), tu((size_t)(L.sol_v - L.sol_u)), tv((size_t)(L.sol_l - L.sol_v)),
       tl((size_t)nl);
   for (size_t r = 0; r < M->subs.size(); ++r) {
     if (int rc = gar_hip_get_solution(M->subs[r], b, xs ? tx.data() : nullptr, us ? tu.data() : nullptr,
@@ -346,8 +342,8 @@ int multi_get_solution(gar_hip_solver *s, int b, double *xs, double *us, double 
 
 int multi_fetch_results(gar_hip_solver *s, int b, int what) {
   gar_multi *M = s->multi;
-  const gar_hip_solver *L = caller_layout(s);
-  const size_t nsol = (size_t)L->sol_doubles, ngain = (size_t)(L->ff_all_doubles + L->fb_all_doubles);
+  const gar::HostLayout &L = caller_layout(s);
+  const size_t nsol = (size_t)L.sol_doubles, ngain = (size_t)(L.ff_all_doubles + L.fb_all_doubles);
   if (!M->h_results) {
     double *h = nullptr;
     const hipError_t e = gar_host_malloc((void **)&h, sizeof(double) * (nsol + ngain), hipHostMallocPortable);
@@ -372,10 +368,10 @@ int multi_fetch_results(gar_hip_solver *s, int b, int what) {
       const SolRange R = multi_sol_range(s, r);
       const double *src = q->h_results;
       double *dst = M->h_results;
-      std::copy(src + L->sol_x + R.x0, src + L->sol_x + R.x1, dst + L->sol_x + R.x0);
-      std::copy(src + L->sol_u + R.u0, src + L->sol_u + R.u1, dst + L->sol_u + R.u0);
-      std::copy(src + L->sol_v + R.v0, src + L->sol_v + R.v1, dst + L->sol_v + R.v0);
-      std::copy(src + L->sol_l + R.l0, src + L->sol_l + R.l1, dst + L->sol_l + R.l0);
+      std::copy(src + L.sol_x + R.x0, src + L.sol_x + R.x1, dst + L.sol_x + R.x0);
+      std::copy(src + L.sol_u + R.u0, src + L.sol_u + R.u1, dst + L.sol_u + R.u0);
+      std::copy(src + L.sol_v + R.v0, src + L.sol_v + R.v1, dst + L.sol_v + R.v0);
+      std::copy(src + L.sol_l + R.l0, src + L.sol_l + R.l1, dst + L.sol_l + R.l0);
     }
   return GAR_HIP_OK;
 }

@@ -118,14 +118,59 @@ template <int NX, int NU> void bind_leg(gar_hip_solver *s) {
   s->kernel_name = "wave_leg<" + std::to_string(NX) + "," + std::to_string(NU) + ">";
 }
 
-// the wide shape in leg mode: segment legs (gar_leg_seg.hpp) on the two-wave stage kernel
+// the wide shape in leg mode: segment legs (gar_leg_seg.hpp) on the two-wave stage kernel -- unconstrained problems
+// (the fold serves the wave-leg family alone) whose parameter stage fits a CU's LDS; GAR_HIP_SEG_LEGS=0: off
 template <int NX, int NU> void bind_seg_leg(gar_hip_solver *s) {
+  for (int t = 0; t <= s->horizon; ++t)
+    if (s->dims5[5 * (size_t)t + 2] != 0)
+      return;
+  const char *sg = gar_option("GAR_HIP_SEG_LEGS");
+  if ((sg && sg[0] == '0') || (size_t)gar::leg_stage_lds_doubles(NX, NU) * sizeof(double) > 160 * 1024)
+    return;
   s->seg_bwd_kernel = gar::gar_backward_pair_leg<NX, NU>;
   s->seg_fwd_kernel = gar::gar_forward_wide_leg<NX, NU>;
   s->seg_lds_doubles = gar::PairCfg<NX, NU>::total;
   s->fb_t2 = false; // row-major fb: the generic roll-out, condensed solve and collapse serve the family
   s->kernel_name = "pair_leg<" + std::to_string(NX) + "," + std::to_string(NU) + ">";
 }
+
+// uniform problems with NC constraints on every knot: the one-wave-per-problem kernels with the
+// reduced KKT system factorised by the wave-scope Bunch-Kaufman (gar_wave.hpp, NC > 0)
+template <int NX, int NU, int NC> void bind_cstr(gar_hip_solver *s) {
+  s->wave_kernel = gar::gar_backward_wave<NX, NU, NC>;
+  s->wave_coupled_kernel = gar::gar_backward_wave_coupled<NX, NU, NC>;
+  s->wave_bk_kernel = gar::gar_backward_wave_bk<NX, NU, NC>;
+  s->mfma_fwd_kernel = gar::gar_forward_mfma<NX, NU, NC>;
+  s->mfma_fwd_lds_bytes = sizeof(double) * (size_t)gar_sym_packed_doubles(NX);
+  s->fb_t2 = true;
+  const int with_init = gar::WaveCfg<NX, NU, NC>::total_with_init(s->nc0);
+  s->wave_fused_init = (size_t)with_init * sizeof(double) <= 64 * 1024 && s->nth0 == 0;
+  s->wave_lds_doubles = s->wave_fused_init ? with_init : gar::WaveCfg<NX, NU, NC>::total;
+  s->waves_per_block = 1;
+  s->kernel_name = "wave<" + std::to_string(NX) + "," + std::to_string(NU) + "," + std::to_string(NC) + ">";
+  s->qr_packed = true; // the chain's three kernels read only the lower triangles of Q and R (gar_layout.h)
+}
+
+// The (nx, nu) shapes with kernels of their own, and what binds them serial in time and in leg mode: select_kernel,
+// select_leg_kernel and choose_padding (which pads onto the cheapest row that holds the caller's shape) all read
+// kSpecialised.  (The constrained segment legs are instantiated in a translation unit of their own and keep the list
+// of their shapes there: gar::cseg_bind, gar_cstr_seg.cpp.)
+using BindFn = void (*)(gar_hip_solver *);
+struct SpecShape { int nx, nu; BindFn bind_serial, bind_leg; };
+struct CstrShape { int nx, nu, nc; BindFn bind; };
+#define GAR_WAVE_SHAPES(X) X(36, 12) X(32, 12) X(16, 8) X(12, 8) X(12, 4) X(8, 4)
+#define GAR_LEG_BINDER(NX, NU) bind_leg<NX, NU>,
+#define GAR_SHAPE_ROW(NX, NU) {NX, NU, bind_mfma<NX, NU>, bind_leg<NX, NU>},
+// (the compiler emits the kernels in the order their binders are first named: the leg families, the constrained ones
+// below, then the serial ones -- this line names the first group ahead of the table's rows and so keeps the code object
+// what it was when two if-chains named them)
+[[maybe_unused]] constexpr BindFn kLegBindersFirst[] = {GAR_WAVE_SHAPES(GAR_LEG_BINDER) bind_seg_leg<56, 24>};
+// the shapes with nc constraints on every knot, serial in time (the reference's bench/gar-riccati.cpp shape)
+constexpr CstrShape kConstrained[] = {{36, 12, 32, bind_cstr<36, 12, 32>}, {16, 8, 8, bind_cstr<16, 8, 8>}, {8, 4, 4, bind_cstr<8, 4, 4>}};
+constexpr SpecShape kSpecialised[] = {GAR_WAVE_SHAPES(GAR_SHAPE_ROW){56, 24, bind_wide<56, 24>, bind_seg_leg<56, 24>}};
+#undef GAR_WAVE_SHAPES
+#undef GAR_LEG_BINDER
+#undef GAR_SHAPE_ROW
 
 // leg mode: uniform unconstrained problem whose every leg holds at least two knots
 void select_leg_kernel(gar_hip_solver *s) {
@@ -154,76 +199,18 @@ void select_leg_kernel(gar_hip_solver *s) {
     if (i1 - i0 < (i + 1 < s->num_legs ? 2 : 1))
       return;
   }
-  if (nx == 36 && nu == 12) bind_leg<36, 12>(s);
-  else if (nx == 32 && nu == 12) bind_leg<32, 12>(s);
-  else if (nx == 16 && nu == 8) bind_leg<16, 8>(s);
-  else if (nx == 12 && nu == 8) bind_leg<12, 8>(s);
-  else if (nx == 12 && nu == 4) bind_leg<12, 4>(s);
-  else if (nx == 8 && nu == 4) bind_leg<8, 4>(s);
-  else if (nx == 56 && nu == 24 && !any_nc) {
-    const char *sg = gar_option("GAR_HIP_SEG_LEGS");
-    if (!(sg && sg[0] == '0') && (size_t)gar::leg_stage_lds_doubles(56, 24) * sizeof(double) <= 160 * 1024)
-      bind_seg_leg<56, 24>(s);
-  }
+  for (const SpecShape &sh : kSpecialised)
+    if (sh.nx == nx && sh.nu == nu)
+      sh.bind_leg(s);
   s->fold = any_nc && s->leg_bwd_kernel != nullptr;
 }
 
-// uniform problems with NC constraints on every knot: the one-wave-per-problem kernels with the
-// reduced KKT system factorised by the wave-scope Bunch-Kaufman (gar_wave.hpp, NC > 0)
-template <int NX, int NU, int NC> void bind_cstr(gar_hip_solver *s) {
-  s->wave_kernel = gar::gar_backward_wave<NX, NU, NC>;
-  s->wave_coupled_kernel = gar::gar_backward_wave_coupled<NX, NU, NC>;
-  s->wave_bk_kernel = gar::gar_backward_wave_bk<NX, NU, NC>;
-  s->mfma_fwd_kernel = gar::gar_forward_mfma<NX, NU, NC>;
-  s->mfma_fwd_lds_bytes = sizeof(double) * (size_t)gar_sym_packed_doubles(NX);
-  s->fb_t2 = true;
-  const int with_init = gar::WaveCfg<NX, NU, NC>::total_with_init(s->nc0);
-  s->wave_fused_init = (size_t)with_init * sizeof(double) <= 64 * 1024 && s->nth0 == 0;
-  s->wave_lds_doubles = s->wave_fused_init ? with_init : gar::WaveCfg<NX, NU, NC>::total;
-  s->waves_per_block = 1;
-  s->kernel_name = "wave<" + std::to_string(NX) + "," + std::to_string(NU) + "," + std::to_string(NC) + ">";
-  s->qr_packed = true; // the chain's three kernels read only the lower triangles of Q and R (gar_layout.h)
-}
-
 void select_kernel(gar_hip_solver *s) {
-  s->fold = false;
-  s->cseg_on = false;
-  s->seg_bwd_kernel = nullptr;
-  s->seg_fwd_kernel = nullptr;
-  s->leg_bwd_kernel = nullptr;
-  s->leg_tuple_kernel = nullptr;
-  s->leg_fwd_kernel = nullptr;
-  s->leg_collapse_kernel = nullptr;
-  s->cond_wave_kernel = nullptr;
-  s->cyc_setup_kernel = nullptr;
-  s->cyc_reduce_kernel = nullptr;
-  s->cyc_top_kernel = nullptr;
-  s->cyc_backlevel_kernel = nullptr;
-  s->cyc_recover_kernel = nullptr;
-  s->mfma_kernel = nullptr;
-  s->mfma_fwd_kernel = nullptr;
-  s->mfma_fwd_lds_bytes = 0;
-  s->wave_kernel = nullptr;
-  s->wave_coupled_kernel = nullptr;
-  s->wave_bk_kernel = nullptr;
-  // (the pipelined sweep's kernels belong to the family bound below: a rebuild for other dimensions must not keep
-  // launching the old shape's half-batch kernels over the new records)
-  s->lean_fwd_kernel = nullptr;
-  s->wave_half_kernel = nullptr;
-  s->lean_fwd_used = 0;
-  s->lean_fwd_lds_bytes = 0;
-  s->wave_lds_doubles_small = 0;
-  s->wave_fused_init = false;
-  s->wave_block_threads = 64;
-  s->fb_t2 = false;
-  s->vxx_packed = false;
-  s->wide_vxx_packed = false;
-  s->qr_packed = false;
+  static_cast<gar::KernelBinding &>(*s) = gar::KernelBinding{}; // nothing of the family bound before survives
   {
     const char *ik = gar_option("GAR_HIP_INIT");
     s->init_closed = !(ik && std::string(ik) == "bk");
   }
-  s->kernel_name = "generic";
   if (s->dense) {
     s->kernel_name = "dense";
     return;
@@ -255,28 +242,18 @@ void select_kernel(gar_hip_solver *s) {
     return;
   const int nx = m0.nx, nu = m0.nu;
   if (m0.nc != 0) { // every knot constrained (the reference's bench/gar-riccati.cpp shape)
-    const int nc = m0.nc;
-    if (nx == 36 && nu == 12 && nc == 32) bind_cstr<36, 12, 32>(s);
-    else if (nx == 16 && nu == 8 && nc == 8) bind_cstr<16, 8, 8>(s);
-    else if (nx == 8 && nu == 4 && nc == 4) bind_cstr<8, 4, 4>(s);
+    for (const CstrShape &sh : kConstrained)
+      if (sh.nx == nx && sh.nu == nu && sh.nc == m0.nc)
+        sh.bind(s);
     s->vxx_packed = s->fb_t2; // (serial one-wave family: gar_layout.h)
     return;
   }
-  if (nx == 36 && nu == 12) bind_mfma<36, 12>(s);
-  else if (nx == 32 && nu == 12) bind_mfma<32, 12>(s);
-  else if (nx == 16 && nu == 8) bind_mfma<16, 8>(s);
-  else if (nx == 12 && nu == 8) bind_mfma<12, 8>(s);
-  else if (nx == 12 && nu == 4) bind_mfma<12, 4>(s);
-  else if (nx == 8 && nu == 4) bind_mfma<8, 4>(s);
-  else if (nx == 56 && nu == 24) bind_wide<56, 24>(s);
+  for (const SpecShape &sh : kSpecialised)
+    if (sh.nx == nx && sh.nu == nu)
+      sh.bind_serial(s);
   // the serial one-wave family keeps the lower triangle of Vxx, packed (gar_layout.h); round 6: the two-wave wide family too
   s->vxx_packed = s->fb_t2 || s->wide_vxx_packed;
 }
-
-// (nx, nu) shapes with kernels of their own (bind_mfma / bind_leg / bind_wide / bind_seg_leg above)
-struct SpecShape { int nx, nu; bool serial_only; };
-constexpr SpecShape kSpecialised[] = {{36, 12, false}, {32, 12, false}, {16, 8, false}, {12, 8, false},
-                                      {12, 4, false}, {8, 4, false},   {56, 24, false}};
 
 // Decide the device dimensions from the caller's (see gar_hip_solver::padded).  GAR_HIP_PAD=0: never pad.
 void choose_padding(gar_hip_solver *s) {
@@ -300,8 +277,6 @@ void choose_padding(gar_hip_solver *s) {
   long best = -1;
   int bx = 0, bu = 0;
   for (const SpecShape &sh : kSpecialised) {
-    if (s->num_legs > 1 && sh.serial_only)
-      continue;
     if (sh.nx == nx && sh.nu == nu)
       return; // the shape has its own kernels
     if (sh.nx >= nx && sh.nu >= nu) {
@@ -349,25 +324,27 @@ int configure(gar_hip_solver *s) {
   }
 }
 
+// A second layout of `src`'s problem: its inputs with one of them changed by `tweak`, laid out
+template <class Tweak> int derive_layout(std::unique_ptr<gar::HostLayout> &out, const gar::HostLayout &src, Tweak tweak) {
+  out = std::make_unique<gar::HostLayout>();
+  out->horizon = src.horizon;
+  out->nc0 = src.nc0;
+  out->num_legs = src.num_legs;
+  out->dense = src.dense;
+  out->dims5 = src.dims5;
+  tweak(*out);
+  return build_layout(*out);
+}
+
 int configure_padded_or_not(gar_hip_solver *s) {
-  if (int rc = build_layout(s))
+  if (int rc = build_layout(*s))
     return rc;
   if (int rc = plan_lds(s))
     return rc;
-  delete s->ulay;
-  s->ulay = nullptr;
-  if (s->padded) {
-    gar_hip_solver *u = new gar_hip_solver();
-    u->horizon = s->horizon;
-    u->batch = s->batch;
-    u->num_legs = s->num_legs;
-    u->dense = s->dense;
-    u->nc0 = s->user_nc0;
-    u->dims5 = s->user_dims5;
-    s->ulay = u;
-    if (int rc = build_layout(u))
+  s->ulay.reset();
+  if (s->padded) // the caller-facing records: the caller's dimensions
+    if (int rc = derive_layout(s->ulay, *s, [s](gar::HostLayout &u) { u.nc0 = s->user_nc0; u.dims5 = s->user_dims5; }))
       return rc;
-  }
   if (s->num_legs > 1) {
     const int J = s->num_legs, W = s->world;
     if (W < 1 || W > J || s->rank < 0 || s->rank >= W)
@@ -386,43 +363,28 @@ int configure_padded_or_not(gar_hip_solver *s) {
   select_kernel(s);
   if (!s->lds_error.empty() && !(s->wave_kernel || s->mfma_kernel || s->leg_bwd_kernel || s->seg_bwd_kernel))
     return fail(GAR_HIP_ERR_UNSUPPORTED, s->lds_error);
-  delete s->flay;
-  s->flay = nullptr;
-  if (s->seg_bwd_kernel) { // scratch records of the plain kernels: the same knots, serial (nth = 0) layout
-    gar_hip_solver *f = new gar_hip_solver();
-    f->horizon = s->horizon;
-    f->batch = s->batch;
-    f->num_legs = 1;
-    f->nc0 = s->nc0;
-    f->dims5 = s->dims5;
-    s->flay = f;
-    if (int rc = build_layout(f))
+  s->flay.reset();
+  if (s->seg_bwd_kernel) // scratch records of the plain kernels: the same knots, serial (nth = 0) layout
+    if (int rc = derive_layout(s->flay, *s, [](gar::HostLayout &f) { f.num_legs = 1; }))
       return rc;
-  }
-  if (s->fold) {
-    gar_hip_solver *f = new gar_hip_solver();
-    f->horizon = s->horizon;
-    f->batch = s->batch;
-    f->num_legs = s->num_legs;
-    f->nc0 = s->nc0;
-    f->dims5 = s->dims5;
-    for (int t = 0; t <= s->horizon; ++t)
-      f->dims5[5 * (size_t)t + 2] = 0;
-    s->flay = f;
-    if (int rc = build_layout(f))
+  if (s->fold) { // the folded problem: the same knots without their constraints
+    auto unconstrained = [](gar::HostLayout &f) {
+      for (int t = 0; t <= f.horizon; ++t)
+        f.dims5[5 * (size_t)t + 2] = 0;
+    };
+    if (int rc = derive_layout(s->flay, *s, unconstrained))
       return rc;
     s->kernel_name += "+fold";
     // problems with D != 0: the constrained segment legs (gar_cstr_seg.hpp) where every knot carries the same number of
     // constraints and the shape has the serial constrained chain; their scratch records live in the flagged problem's
     // slice of the wave-leg family's factor buffer
-    s->cseg_on = false;
     const char *cs = gar_option("GAR_HIP_CSTR_SEG_LEGS");
     const int nx = s->dims5[0], nu = s->dims5[1], nc = s->dims5[2];
     bool uniform_nc = nc > 0;
     for (int t = 0; t <= s->horizon; ++t)
       uniform_nc &= s->dims5[5 * (size_t)t + 2] == nc;
     if (uniform_nc && !(cs && cs[0] == '0') && gar::cseg_bind(nx, nu, nc, &s->cseg) &&
-        s->cseg.scratch_doubles(s->horizon, s->num_legs) <= f->fac_doubles) {
+        s->cseg.scratch_doubles(s->horizon, s->num_legs) <= s->flay->fac_doubles) {
       s->cseg_on = true;
       s->qr_packed = true; // the chain's kernels read only the lower triangles of Q and R (gar_layout.h); the fold unpacks
       s->kernel_name += "|wave_seg<" + std::to_string(nx) + "," + std::to_string(nu) + "," + std::to_string(nc) + ">";
