@@ -117,34 +117,6 @@ struct RoctxRange {
 // Every entry point runs on the solver's own device, whatever the caller's current device is, and
 // leaves the caller's current device as it found it (two solvers on two GPUs in one process;
 // torch's notion of the current device).
-// Behaviour switches (kernel family, padding, condensed solver, ...): `GAR_HIP_*` names, looked up in the overrides
-// set through gar_hip_set_option first, in the environment second.  Most are read when a solver is created
-// (family selection), some per launch (GAR_HIP_SPD_ACCEPT) -- include/gar_hip.h lists them.
-std::mutex &option_mutex() {
-  static std::mutex m;
-  return m;
-}
-std::map<std::string, std::string> &option_overrides() {
-  static std::map<std::string, std::string> o;
-  return o;
-}
-const char *gar_option(const char *name) {
-  // (the value is copied out under the lock into a per-thread slot: a concurrent gar_hip_set_option cannot pull the
-  // string from under the caller; eight slots cover every use that holds more than one option at a time)
-  thread_local std::string slot[8];
-  thread_local unsigned next = 0;
-  {
-    std::lock_guard<std::mutex> g(option_mutex());
-    auto it = option_overrides().find(name);
-    if (it != option_overrides().end()) {
-      std::string &v = slot[next++ & 7u];
-      v = it->second;
-      return v.c_str();
-    }
-  }
-  return std::getenv(name);
-}
-
 void pipe_autojoin(const gar_hip_solver *s);
 struct DeviceGuard {
   int prev = -1, dev;
@@ -284,6 +256,16 @@ struct gar_hip_solver : gar::HostLayout, gar::KernelBinding {
 };
 
 namespace {
+
+// The status buffer (d_status, ints) has three regions:
+//   [0, batch)                      status_words: a word per problem, 0 = the last sweep succeeded
+//   [batch, batch + 4)              status_counters: MfmaParams::slow -- slow-path stages (2), constrained stages (2)
+//   [batch + 4, 2 batch + 4)        status_flags: a word per problem -- MfmaParams::resume; folded solvers: "flagged, D != 0"
+constexpr int kStatusCounters = 4;
+inline int *status_words(const gar_hip_solver *s, int b0 = 0) { return s->d_status + b0; }
+inline int *status_counters(const gar_hip_solver *s) { return s->d_status + s->batch; }
+inline int *status_flags(const gar_hip_solver *s) { return s->d_status + s->batch + kStatusCounters; }
+inline size_t status_bytes(size_t b, bool flags) { return sizeof(int) * (b + kStatusCounters + (flags ? b : 0)); }
 
 // ---- layout ---------------------------------------------------------------
 int build_layout(gar::HostLayout &s) {
@@ -710,34 +692,33 @@ int write_block(gar_hip_solver *s, int b, int64_t off, const double *src, int64_
 // the condensed solve's info slots (residual, steps, scale, resolved) in a problem's scratch: behind its blocks
 inline int64_t cond_info_off(const gar_hip_solver *s) { return 4 * (int64_t)(2 * s->num_legs) * ((int64_t)s->nxb * s->nxb + s->nxb); }
 
+// MfmaParams, what every fill shares: the knot records of layout `in` (the solver's own or the folded one), the factor
+// records, the status words and counters, the horizon.  mueq and spd_accept belong to the stage sweeps (gar_launch.hpp:
+// make_mfma_scratch_params); the wave-leg family's embedded block leaves them at zero.
+gar::MfmaParams mfma_common(gar_hip_solver *s, const gar::HostLayout &in, const double *prob, double *fac, long long fac_stride) {
+  gar::MfmaParams M{};
+  M.prob = prob;
+  M.fac = fac;
+  M.status = status_words(s);
+  M.slow = status_counters(s);
+  M.prob_stride = in.prob_doubles;
+  M.fac_stride = fac_stride;
+  M.in_off0 = in.uni_in0;
+  M.in_rec = in.uni_in_rec;
+  M.in_offN = in.meta[in.horizon].in_off;
+  M.horizon = in.horizon;
+  return M;
+}
+
 gar::LegParams make_leg_params(gar_hip_solver *s) {
   gar::LegParams Q{};
-  const int N = s->horizon;
-  Q.M.prob = s->d_prob;
-  Q.M.fac = s->d_fac;
-  Q.M.status = s->d_status;
-  Q.M.slow = s->d_status + s->batch;
-  Q.M.prob_stride = s->prob_doubles;
-  Q.M.fac_stride = s->fac_doubles;
-  Q.M.in_off0 = s->uni_in0;
-  Q.M.in_rec = s->uni_in_rec;
-  Q.M.in_offN = s->meta[N].in_off;
-  Q.M.horizon = N;
+  // folded solvers: the wave-leg family sweeps the folded knots and keeps its own (nc = 0) factor records; problems
+  // with D != 0 are skipped (the generic leg kernels or the constrained segment legs take them)
+  Q.M = s->fold ? mfma_common(s, *s->flay, s->d_prob2, s->d_fac2, s->flay->fac_doubles)
+                : mfma_common(s, *s, s->d_prob, s->d_fac, s->fac_doubles);
   Q.M.trace = s->d_trace;
-  Q.meta = s->d_meta;
-  Q.skip = nullptr;
-  if (s->fold) { // the wave-leg family sweeps the folded knots and keeps its own (nc = 0) factor records
-    const gar::HostLayout &f = *s->flay;
-    Q.M.prob = s->d_prob2;
-    Q.M.fac = s->d_fac2;
-    Q.M.prob_stride = f.prob_doubles;
-    Q.M.fac_stride = f.fac_doubles;
-    Q.M.in_off0 = f.uni_in0;
-    Q.M.in_rec = f.uni_in_rec;
-    Q.M.in_offN = f.meta[N].in_off;
-    Q.meta = s->d_meta2;
-    Q.skip = s->d_status + s->batch + 4; // problems with D != 0: the generic leg kernels take them
-  }
+  Q.meta = s->fold ? s->d_meta2 : s->d_meta;
+  Q.skip = s->fold ? status_flags(s) : nullptr;
   Q.num_legs = s->num_legs;
   Q.leg_begin = s->leg_begin;
   Q.csol = s->d_csol;
@@ -777,7 +758,7 @@ gar::FoldParams make_fold_params(gar_hip_solver *s) {
   F.fac_stride = s->fac_doubles;
   F.fac2_stride = f.fac_doubles;
   F.sol_stride = s->sol_doubles;
-  F.coupled = s->d_status + s->batch + 4;
+  F.coupled = status_flags(s);
   F.horizon = s->horizon;
   F.t2 = s->fb_t2 ? 1 : 0;
   int lo, hi, dummy;
@@ -805,7 +786,7 @@ int ensure_expanded(gar_hip_solver *s) {
   }
   if (!s->coupled_known) {
     s->h_coupled.assign((size_t)s->batch, 0);
-    HIP_TRY(hipMemcpyAsync(s->h_coupled.data(), s->d_status + s->batch + 4, sizeof(int) * (size_t)s->batch,
+    HIP_TRY(hipMemcpyAsync(s->h_coupled.data(), status_flags(s), sizeof(int) * (size_t)s->batch,
                            hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->coupled_known = true;
@@ -883,8 +864,7 @@ int allocate(gar_hip_solver *s) {
   HIP_TRY(dev_zalloc(&s->d_sol, sizeof(double) * (size_t)s->sol_doubles * B));
   HIP_TRY(dev_zalloc(&s->d_init, sizeof(double) * (size_t)s->init_doubles * B));
   HIP_TRY(gar_dev_malloc((void **)&s->d_theta, sizeof(double) * (size_t)std::max(s->nth0, 1) * B));
-  // per-problem failure flags, then the four slow-path counters (MfmaParams::slow), then MfmaParams::resume
-  HIP_TRY(dev_zalloc(&s->d_status, sizeof(int) * (2 * B + 4)));
+  HIP_TRY(dev_zalloc(&s->d_status, status_bytes(B, true))); // (the three regions: status_words)
   if (s->num_legs > 1) {
     const int chunk = s->legs_per_rank; // >= this rank's own leg count; equal-sized chunks for the all-gather
     const int nblk = 2 * s->num_legs;
@@ -905,8 +885,7 @@ int allocate(gar_hip_solver *s) {
     HIP_TRY(dev_zalloc(&s->d_cscratch, sizeof(double) * (size_t)s->cscratch_doubles * B));
     s->cond_lds_doubles = (int)(3 * bs + 4 * s->nxb + 2 + (s->nxb + 16) / 2 + 2 + (s->nxb < 9 ? 9 * s->nxb : 0));
     {
-      const char *cr = gar_option("GAR_HIP_CONDENSED_REDUCED");
-      s->cond_reduced = !(cr && cr[0] == '0') && s->nx0 == s->nxb &&
+      s->cond_reduced = !option_off("GAR_HIP_CONDENSED_REDUCED") && s->nx0 == s->nxb &&
                         (size_t)gar::gar_condensed_leg_lds_doubles(s->nxb) * sizeof(double) <= 160 * 1024;
       // cyclic reduction of the reduced system: log2 J dependent steps instead of J; below 4 legs the chain is as short
       const char *cc = gar_option("GAR_HIP_CONDENSED_CR");
@@ -1567,7 +1546,7 @@ int gar_hip_backward_legs_async(gar_hip_solver *s, double mueq) {
   }
   if (int rc = commit(s))
     return rc;
-  HIP_TRY(hipMemsetAsync(s->d_status, 0, sizeof(int) * ((size_t)s->batch + 4 + (s->fold ? (size_t)s->batch : 0)), s->stream));
+  HIP_TRY(hipMemsetAsync(status_words(s), 0, status_bytes((size_t)s->batch, s->fold), s->stream));
   return launch_backward(s, mueq);
 }
 
@@ -1749,8 +1728,8 @@ int gar_hip_backward_blocks(gar_hip_solver *s, const double *const *blocks, cons
   // sweep, with the solution's copy and the gains' read-back (second stream), BEFORE the host waits for the status
   // word -- the device runs sweep, roll-out and copies back to back instead of waiting for the host between them.
   // gar_hip_forward / gar_hip_prefetch_gains / the solution fetch then find their work done.
-  const bool eager_on = [] { const char *e = gar_option("GAR_HIP_EAGER"); return !(e && e[0] == '0'); }();
-  const bool eager = eager_on && !s->multi && !s->fold && !s->dense && (s->nth0 == 0 || s->num_legs > 1) && s->world == 1;
+  const bool eager = !option_off("GAR_HIP_EAGER") && !s->multi && !s->fold && !s->dense &&
+                     (s->nth0 == 0 || s->num_legs > 1) && s->world == 1;
   if (!eager)
     return gar_hip_backward(s, mueq);
   if (int rc = gar_hip_backward_legs_async(s, mueq))
@@ -1828,7 +1807,7 @@ int gar_hip_slow_path_stages(gar_hip_solver *s, int64_t out[2]) {
   if (!s || !out)
     return fail(GAR_HIP_ERR_ARG, "bad argument");
   int c[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(c, s->d_status + s->batch, sizeof(c), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(c, status_counters(s), sizeof(c), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   out[0] = c[0];
   out[1] = c[1];
@@ -1841,7 +1820,7 @@ int gar_hip_constrained_bk_stages(gar_hip_solver *s, int64_t out[2]) {
   if (!s || !out)
     return fail(GAR_HIP_ERR_ARG, "bad argument");
   int c[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(c, s->d_status + s->batch + 2, sizeof(c), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(c, status_counters(s) + 2, sizeof(c), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   out[0] = c[0];
   out[1] = c[1];
@@ -2439,7 +2418,7 @@ int gar_hip_collapse_feedback(gar_hip_solver *s) {
   if (s->num_legs < 2 || s->leg_begin != 0)
     return GAR_HIP_OK; // no-op except Parallel (riccati-base.hpp:33)
   if (s->fold) { // the wave-leg family's own records (then re-expanded on request); flagged problems: generic records
-    const int *flags = s->d_status + s->batch + 4;
+    const int *flags = status_flags(s);
     hipLaunchKernelGGL(s->leg_collapse_kernel, dim3((unsigned)s->batch), dim3(256), 0, s->stream, s->d_meta2, s->d_fac2,
                        (long long)s->flay->fac_doubles, s->batch, flags, 0);
     hipLaunchKernelGGL(gar::gar_collapse_feedback, dim3((unsigned)s->batch), dim3(256), 0, s->stream, s->d_meta, s->d_fac,

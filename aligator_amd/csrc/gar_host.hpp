@@ -1,9 +1,46 @@
 // gar_host.hpp -- the two parts of the solver handle (gar_hip.cpp: gar_hip_solver derives from both) that are not run
 // state: the record layout of one problem (HostLayout: build_layout fills it; the caller-facing and the scratch
 // layouts of a solver are bare ones) and the kernel family bound to it (KernelBinding: select_kernel resets it by value
-// and the bind_* functions of gar_select.hpp fill it).  Included by gar_hip.cpp behind the kernel headers; internal
-// linkage, like the rest of that translation unit's host code: the library exports nothing of them.
+// and the bind_* functions of gar_select.hpp fill it).  Included by gar_hip.cpp behind its standard headers (<cstdlib>,
+// <cstring>, <map>, <mutex>, <string>, <vector>: none is included here) and the kernel headers; internal linkage, like
+// the rest of that unit's host code.  Ahead of them: gar_option and its two predicates, which need nothing of a solver.
 #pragma once
+
+namespace {
+// Behaviour switches (kernel family, padding, condensed solver, ...): `GAR_HIP_*` names, looked up in the overrides
+// set through gar_hip_set_option first, in the environment second.  Most are read when a solver is created
+// (family selection), some per launch (GAR_HIP_SPD_ACCEPT) -- include/gar_hip.h lists them.
+std::mutex &option_mutex() {
+  static std::mutex m;
+  return m;
+}
+std::map<std::string, std::string> &option_overrides() {
+  static std::map<std::string, std::string> o;
+  return o;
+}
+const char *gar_option(const char *name) {
+  // (the value is copied out under the lock into a per-thread slot: a concurrent gar_hip_set_option cannot pull the
+  // string from under the caller; eight slots cover every use that holds more than one option at a time)
+  thread_local std::string slot[8];
+  thread_local unsigned next = 0;
+  {
+    std::lock_guard<std::mutex> g(option_mutex());
+    auto it = option_overrides().find(name);
+    if (it != option_overrides().end()) {
+      std::string &v = slot[next++ & 7u];
+      v = it->second;
+      return v.c_str();
+    }
+  }
+  return std::getenv(name);
+}
+// the two tests most switches are read with: "NAME=0 turns it off" (first character) and "NAME=word"
+inline bool option_off(const char *name) { const char *v = gar_option(name); return v && v[0] == '0'; }
+inline bool option_is(const char *name, const char *word) {
+  const char *v = gar_option(name);
+  return v && std::strcmp(v, word) == 0;
+}
+} // namespace
 
 namespace gar {
 namespace {
@@ -82,7 +119,7 @@ struct KernelBinding {
   void (*seg_fwd_kernel)(GenericParams) = nullptr; // its roll-out (gar_forward_wide_leg), leg mode
   int seg_lds_doubles = 0;
   // Constrained knots (nc > 0) in leg mode on the unconstrained wave-leg kernels (gar_fold.hpp): problems with D != 0
-  // are flagged on the device (d_status + batch + 4) and taken by the generic leg kernels ...
+  // are flagged on the device (status_flags, gar_hip.cpp) and taken by the generic leg kernels ...
   bool fold = false;
   // ... unless the shape has the constrained segment legs (gar_cstr_seg.hpp, round 6): then the flagged problems run
   // on the serial constrained chain's stage kernels, leg by leg, + a parameter recursion; the knots keep Q, R packed

@@ -495,8 +495,7 @@ gar_hip_solver *multi_create(int ndev, const int *dev_ids, int horizon, const in
       if (hipDeviceCanAccessPeer(&can, dev_ids[r], dev_ids[p]) != hipSuccess || !can)
         peers = false;
     }
-  const char *ex = gar_option("GAR_HIP_MULTI_EXCHANGE");
-  const bool want_copy = ex && std::string(ex) == "copy";
+  const bool want_copy = option_is("GAR_HIP_MULTI_EXCHANGE", "copy");
   if (peers && !want_copy)
     for (int r = 0; r < ndev && peers; ++r) {
       DeviceGuard g(dev_ids[r]);

@@ -82,9 +82,9 @@ int pipe_backward(gar_hip_solver *s, double mueq) {
     // which is also when that half's forward sweep starts (its stream's next kernel)
     if (s->pipe_evB_valid[1 - h])
       HIP_TRY(hipStreamWaitEvent(st, s->pipe_evB[1 - h], 0));
-    HIP_TRY(hipMemsetAsync(s->d_status + b0, 0, sizeof(int) * (size_t)nb, st));
+    HIP_TRY(hipMemsetAsync(status_words(s, b0), 0, sizeof(int) * (size_t)nb, st));
     if (h == 0) // the slow-path counters of "the last backward" cover both halves (the second half runs behind this one)
-      HIP_TRY(hipMemsetAsync(s->d_status + s->batch, 0, sizeof(int) * 4, st));
+      HIP_TRY(hipMemsetAsync(status_counters(s), 0, sizeof(int) * kStatusCounters, st));
     gar::MfmaParams M = M0;
     M.prob += (long long)b0 * M.prob_stride;
     M.fac += (long long)b0 * M.fac_stride;

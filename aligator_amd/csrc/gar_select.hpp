@@ -15,14 +15,14 @@ template <int NX, int NU> void bind_mfma(gar_hip_solver *s) {
   // one 4-wave workgroup per problem (latency: a problem gets a whole CU; measured 2.2 ms vs
   // 3.0 ms per sweep while there are no more problems than CUs).  GAR_HIP_BACKWARD=wave|wg4
   // overrides the choice.
-  const char *bw = gar_option("GAR_HIP_BACKWARD");
+  const char *bw = gar_option("GAR_HIP_BACKWARD"); // (read once: unset, wg4, pair and anything else all matter)
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
-  const bool want_wave = bw ? std::string(bw) != "wg4" : s->batch > cus;
+  const bool want_wave = bw ? std::strcmp(bw, "wg4") != 0 : s->batch > cus;
   // GAR_HIP_BACKWARD=pair: two waves per problem, the tile columns split between them
   // (gar_wave_pair.hpp; <= 256 registers per wave, so two waves share a SIMD)
   constexpr bool can_pair = (NX % 16) != 0 && ((NX >> 4) >= (gar::WaveCfg<NX, NU>::TW / 2)) && (gar::WaveCfg<NX, NU>::TW / 2) >= 1;
-  if (bw && std::string(bw) == "pair" && can_pair) {
+  if (bw && std::strcmp(bw, "pair") == 0 && can_pair) {
     if constexpr (can_pair) {
       s->wave_kernel = gar::gar_backward_pair<NX, NU>;
       s->wave_fused_init = false;
@@ -55,9 +55,8 @@ template <int NX, int NU> void bind_mfma(gar_hip_solver *s) {
 // and the forward sweep on the generic kernels.
 template <int NX, int NU> void bind_wide(gar_hip_solver *s) {
   // two waves per problem (the tile columns split between them) unless GAR_HIP_WIDE=single
-  const char *w = gar_option("GAR_HIP_WIDE");
-  const bool pair = !(w && std::string(w) == "single");
-  const bool generic_fwd = w && std::string(w) == "generic-forward";
+  const bool pair = !option_is("GAR_HIP_WIDE", "single");
+  const bool generic_fwd = option_is("GAR_HIP_WIDE", "generic-forward");
   if (!generic_fwd)
     s->mfma_fwd_kernel = gar::gar_forward_wide<NX, NU>; // row-major fb: fb_t2 stays false
   s->wave_fused_init = false;
@@ -90,22 +89,20 @@ template <int NX, int NU> void bind_wide(gar_hip_solver *s) {
 template <int NX, int NU> void bind_leg(gar_hip_solver *s) {
   s->fb_t2 = true;
   // two waves per leg (plain part / parameter part) unless GAR_HIP_LEG_WAVES=1
-  const char *lw = gar_option("GAR_HIP_LEG_WAVES");
-  s->leg_waves = (lw && std::string(lw) == "1") ? 1 : 2;
+  s->leg_waves = option_is("GAR_HIP_LEG_WAVES", "1") ? 1 : 2;
   s->leg_bwd_kernel = s->leg_waves == 2 ? gar::gar_backward_wave_leg2<NX, NU> : gar::gar_backward_wave_leg<NX, NU>;
   s->leg_tuple_kernel = gar::gar_leg_tuples<NX, NU>;
   s->leg_fwd_kernel = gar::gar_forward_wave_leg<NX, NU>;
   s->leg_collapse_kernel = gar::gar_collapse_feedback_t2<NX, NU>;
   s->leg_lds_doubles = s->leg_waves == 2 ? gar::WaveCfg<NX, NU>::leg2_total : gar::WaveCfg<NX, NU>::leg_total;
-  const char *ck = gar_option("GAR_HIP_CONDENSED");
-  if (!(ck && std::string(ck) == "generic")) {
+  if (!option_is("GAR_HIP_CONDENSED", "generic")) {
     const int lds = 4 * NX * NX + 16 * NX + NX + NX + (NX & 1) + (NX + 16) / 2 + 2 +
                     2 * (2 * s->num_legs) * NX + 2;
     if ((size_t)lds * sizeof(double) <= 160 * 1024) {
       s->cond_wave_kernel = gar::gar_condensed_wave<NX>;
       s->cond_wave_lds_doubles = lds;
     }
-    if (!(ck && std::string(ck) == "chain")) {
+    if (!option_is("GAR_HIP_CONDENSED", "chain")) {
       s->cyc_setup_kernel = gar::gar_cyclic_setup<NX>;
       s->cyc_reduce_kernel = gar::gar_cyclic_reduce<NX>;
       s->cyc_top_kernel = gar::gar_cyclic_top<NX>;
@@ -124,8 +121,7 @@ template <int NX, int NU> void bind_seg_leg(gar_hip_solver *s) {
   for (int t = 0; t <= s->horizon; ++t)
     if (s->dims5[5 * (size_t)t + 2] != 0)
       return;
-  const char *sg = gar_option("GAR_HIP_SEG_LEGS");
-  if ((sg && sg[0] == '0') || (size_t)gar::leg_stage_lds_doubles(NX, NU) * sizeof(double) > 160 * 1024)
+  if (option_off("GAR_HIP_SEG_LEGS") || (size_t)gar::leg_stage_lds_doubles(NX, NU) * sizeof(double) > 160 * 1024)
     return;
   s->seg_bwd_kernel = gar::gar_backward_pair_leg<NX, NU>;
   s->seg_fwd_kernel = gar::gar_forward_wide_leg<NX, NU>;
@@ -175,8 +171,7 @@ constexpr SpecShape kSpecialised[] = {GAR_WAVE_SHAPES(GAR_SHAPE_ROW){56, 24, bin
 // leg mode: uniform unconstrained problem whose every leg holds at least two knots
 void select_leg_kernel(gar_hip_solver *s) {
   const int N = s->horizon;
-  const char *lk = gar_option("GAR_HIP_LEGS");
-  if (lk && std::string(lk) == "generic")
+  if (option_is("GAR_HIP_LEGS", "generic"))
     return;
   if (N < 1 || s->nxb != s->dims5[0])
     return;
@@ -190,8 +185,7 @@ void select_leg_kernel(gar_hip_solver *s) {
   }
   // constrained knots: folded onto the unconstrained family (gar_fold.hpp); the generic leg kernels are the
   // fallback for problems with D != 0, so they must fit a CU's LDS
-  const char *fe = gar_option("GAR_HIP_FOLD");
-  if (any_nc && (!s->lds_error.empty() || (fe && fe[0] == '0')))
+  if (any_nc && (!s->lds_error.empty() || option_off("GAR_HIP_FOLD")))
     return;
   for (int i = 0; i < s->num_legs; ++i) {
     int i0, i1;
@@ -207,10 +201,7 @@ void select_leg_kernel(gar_hip_solver *s) {
 
 void select_kernel(gar_hip_solver *s) {
   static_cast<gar::KernelBinding &>(*s) = gar::KernelBinding{}; // nothing of the family bound before survives
-  {
-    const char *ik = gar_option("GAR_HIP_INIT");
-    s->init_closed = !(ik && std::string(ik) == "bk");
-  }
+  s->init_closed = !option_is("GAR_HIP_INIT", "bk");
   if (s->dense) {
     s->kernel_name = "dense";
     return;
@@ -261,9 +252,8 @@ void choose_padding(gar_hip_solver *s) {
   s->nc0 = s->user_nc0;
   s->padded = false;
   s->unx = s->unu = s->pnx = s->pnu = 0;
-  const char *pe = gar_option("GAR_HIP_PAD");
   const int N = s->horizon;
-  if (s->dense || (pe && pe[0] == '0') || N < 1)
+  if (s->dense || option_off("GAR_HIP_PAD") || N < 1)
     return;
   const int32_t *d0 = &s->user_dims5[0];
   const int nx = d0[0], nu = d0[1];
@@ -378,12 +368,11 @@ int configure_padded_or_not(gar_hip_solver *s) {
     // problems with D != 0: the constrained segment legs (gar_cstr_seg.hpp) where every knot carries the same number of
     // constraints and the shape has the serial constrained chain; their scratch records live in the flagged problem's
     // slice of the wave-leg family's factor buffer
-    const char *cs = gar_option("GAR_HIP_CSTR_SEG_LEGS");
     const int nx = s->dims5[0], nu = s->dims5[1], nc = s->dims5[2];
     bool uniform_nc = nc > 0;
     for (int t = 0; t <= s->horizon; ++t)
       uniform_nc &= s->dims5[5 * (size_t)t + 2] == nc;
-    if (uniform_nc && !(cs && cs[0] == '0') && gar::cseg_bind(nx, nu, nc, &s->cseg) &&
+    if (uniform_nc && !option_off("GAR_HIP_CSTR_SEG_LEGS") && gar::cseg_bind(nx, nu, nc, &s->cseg) &&
         s->cseg.scratch_doubles(s->horizon, s->num_legs) <= s->flay->fac_doubles) {
       s->cseg_on = true;
       s->qr_packed = true; // the chain's kernels read only the lower triangles of Q and R (gar_layout.h); the fold unpacks

@@ -167,7 +167,7 @@ def _leg_solution(probs, legs, mueq, refine=None, threshold=1e-10, backward_ok=N
     return s, [s.solution(b) for b in range(len(probs))]
 
 
-@pytest.mark.parametrize("legs,horz,nx,nu", [(6, 17, 8, 4), (4, 7, 12, 4)])
+@pytest.mark.parametrize("legs,horz,nx,nu", [(6, 17, 8, 4), (4, 7, 12, 4), (16, 33, 8, 4)])  # 16 legs: a back-substitution level of its own
 def test_condensed_cyclic_reduction_vs_chain_vs_generic(monkeypatch, legs, horz, nx, nu):
     """Three solvers of the leg-boundary system -- block cyclic reduction (csrc/gar_cyclic.hpp, the
     default, here WITHOUT its fallback: refinement off), the wave-scope elimination chain and the
@@ -1038,6 +1038,67 @@ def test_behaviour_switches_through_the_api():
         set_option("BACKWARD", None, EMU)
         set_option("FORCE_GENERIC", None, EMU)
     assert kernel()[0] == base
+
+
+def _solve(s, mueq):
+    assert s.backward(mueq) and s.forward()
+    return [s.solution(b) for b in range(s.batch)]
+
+
+def _same_bits(A, B):
+    return all(np.array_equal(x, y) for P, Q in zip(A, B) for X, Y in zip(P, Q) for x, y in zip(X, Y))
+
+
+def test_lean_roll_out_in_the_plain_schedule(monkeypatch):
+    """GAR_HIP_FORWARD=lean (read per launch): the pipelined schedule's roll-out (gar_forward_lean.hpp) for the whole
+    batch in the PLAIN schedule -- a workgroup per four problems, here one full and one with a single problem -- gives
+    the default roll-out's solution bit for bit."""
+    from aligator_amd.gar import BatchedRiccatiSolver
+    nx, nu, N = 8, 4, 5
+    probs = [synth.generate_lq_problem(60 + i, np.ones(nx), N, nx, nu, mode="W") for i in range(5)]
+    s = BatchedRiccatiSolver([k.dims for k in probs[0].stages], nx, batch=5, lib_path=EMU)
+    assert s.kernel_name == "wave<8,4>"
+    s.set_pipeline(0)
+    s.upload(probs)
+    default = _solve(s, 1e-10)
+    monkeypatch.setenv("GAR_HIP_FORWARD", "lean")
+    assert _same_bits(_solve(s, 1e-10), default)
+    _, _, ref = pc.oracle_serial(probs[4], 1e-10)
+    for A, B in zip(default[4], ref):
+        assert pc.maxdiff(A, B) <= 1e-9 * pc.scale_of(ref)
+    s.close()
+
+
+def test_timing_events_change_no_result(monkeypatch):
+    """gar_hip_set_timing(s, 1) brackets the launches of every family with events and nothing else: wave legs with the
+    fold and the constrained segment legs, segment legs, the serial one-wave sweep (fused initial stage) and the
+    4-wave one (initial stage launched), each with its roll-out and, in leg mode, the condensed solve -- same bits as
+    with timing off, and gar_hip_last_kernel_ms answers."""
+    import ctypes as C
+    from aligator_amd.gar import BatchedRiccatiSolver
+    rng = np.random.default_rng(12)
+    coupled = synth.generate_lq_problem(rng, rng.standard_normal(8), 5, 8, 4, nc=4, mode="W")
+    coupled.stages[1].D[...] = rng.uniform(-1, 1, coupled.stages[1].D.shape)
+    cases = [(coupled, 3, 1e-6, None, "wave_leg<8,4>+fold"),
+             (synth.generate_lq_problem(rng, np.ones(56), 5, 56, 24, mode="W"), 2, 1e-10, None, "pair_leg<56,24>"),
+             (synth.generate_lq_problem(rng, np.ones(8), 3, 8, 4, mode="W"), 1, 1e-10, "wave", "wave<8,4>"),
+             (synth.generate_lq_problem(rng, np.ones(8), 3, 8, 4, mode="W"), 1, 1e-10, "wg4", "mfma<8,4>")]
+    for prob, legs, mueq, backward, kernel in cases:
+        if backward:
+            monkeypatch.setenv("GAR_HIP_BACKWARD", backward)
+        else:
+            monkeypatch.delenv("GAR_HIP_BACKWARD", raising=False)
+        s = BatchedRiccatiSolver([k.dims for k in prob.stages], prob.nc0, batch=1, num_legs=legs, lib_path=EMU)
+        assert s.kernel_name.startswith(kernel), s.kernel_name
+        s.set_pipeline(0)
+        s.upload([prob])
+        plain = _solve(s, mueq)
+        s._check(s._L.gar_hip_set_timing(s.handle, 1))
+        assert _same_bits(_solve(s, mueq), plain)
+        ms = (C.c_double * 3)()
+        s._check(s._L.gar_hip_last_kernel_ms(s.handle, ms))
+        assert all(np.isfinite(v) and v >= 0.0 for v in ms)
+        s.close()
 
 
 # ---- mueq from 0 to 1: every family against the reference's own rule (tests/parity_cases.py, MUEQ_ROWS) ----------------
