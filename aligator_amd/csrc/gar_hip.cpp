@@ -771,6 +771,16 @@ gar::FoldParams make_fold_params(gar_hip_solver *s) {
   F.lds = fold_lds_bytes(s) > 0 ? 1 : 0;
   return F;
 }
+// the serial twin's kernels (gar_fold_serial, gar_expand_serial): the bound family's own record formats on top
+gar::SerialFoldParams make_serial_fold_params(gar_hip_solver *s) {
+  gar::SerialFoldParams S{};
+  S.F = make_fold_params(s);
+  S.out_qr_packed = s->sf_qr_packed ? 1 : 0;
+  S.src_t2 = s->sf_fb_t2 ? 1 : 0;
+  S.src_vxx_packed = s->sf_vxx_packed ? 1 : 0;
+  S.header = (int)std::min(s->uni_in0, s->flay->uni_in0);
+  return S;
+}
 
 // Folded solvers (gar_hip_solver::fold): the caller-visible factor records are formed on first request after a
 // backward (nobody who only reads the solution pays for them), and which problems the generic kernels took
@@ -779,8 +789,11 @@ int ensure_expanded(gar_hip_solver *s) {
   if (!s->fold)
     return GAR_HIP_OK;
   if (!s->fold_expanded) {
-    hipLaunchKernelGGL(gar::gar_expand_constrained, dim3((unsigned)(s->horizon + 1), (unsigned)s->batch), dim3(256), 0,
-                       s->stream, make_fold_params(s));
+    const dim3 grid((unsigned)(s->horizon + 1), (unsigned)s->batch);
+    if (s->serial_fold)
+      hipLaunchKernelGGL(gar::gar_expand_serial, grid, dim3(256), 0, s->stream, make_serial_fold_params(s));
+    else
+      hipLaunchKernelGGL(gar::gar_expand_constrained, grid, dim3(256), 0, s->stream, make_fold_params(s));
     HIP_TRY(hipGetLastError());
     s->fold_expanded = true;
   }
@@ -1573,7 +1586,7 @@ int gar_hip_set_option(const char *name, const char *value) {
   if (key.rfind("GAR_HIP_", 0) != 0)
     key = "GAR_HIP_" + key;
   static const char *known[] = {"BACKWARD", "WIDE", "LEG_WAVES", "CONDENSED", "CONDENSED_REDUCED", "CONDENSED_CR", "LEGS",
-                                "FOLD", "SEG_LEGS", "INIT", "FORCE_GENERIC", "PAD", "SPD_ACCEPT", "STAGE_NT", "EAGER",
+                                "FOLD", "SERIAL_FOLD", "SEG_LEGS", "INIT", "FORCE_GENERIC", "PAD", "SPD_ACCEPT", "STAGE_NT", "EAGER",
                                 "MULTI_EXCHANGE", "PIPE_PRIORITY", "FORWARD", "PIPELINE", "CSTR_SEG_LEGS",
                                 "CSTR_SEG_LEG_END", "CSTR_SEG_FORWARD"};
   bool ok = false;
@@ -1601,7 +1614,7 @@ namespace {
 bool pipe_eligible(const gar_hip_solver *s) {
   return !(s->multi || s->world > 1 || s->num_legs != 1 || s->nth0 != 0 || s->batch < 2 || !s->wave_kernel || !s->lean_fwd_kernel ||
            !s->wave_half_kernel || s->wave_coupled_kernel || s->wave_block_threads != 64 || s->waves_per_block != 1 || !s->vxx_packed ||
-           s->dense);
+           s->dense || s->serial_fold);
 }
 // The library's own choice of schedule (GAR_HIP_PIPELINE = auto, the default): the pipelined sweep pays by the tails
 // it hides -- the forward sweep of one half starts while the other half's backward sweep still runs -- and only once
@@ -2475,6 +2488,20 @@ int gar_hip_cycle_append(gar_hip_solver *s, const int32_t d[5]) {
     }
     HIP_TRY(hipMemcpyAsync(s->d_meta, s->meta.data(), sizeof(gar_stage_meta) * s->meta.size(),
                            hipMemcpyHostToDevice, s->stream));
+    if (s->serial_fold) { // the folded layout turns with the caller's: the family's records stay where they are too
+      gar::HostLayout &f = *s->flay;
+      f.ring0 = s->ring0;
+      for (int t = 0; t < N; ++t) {
+        const int64_t p = (t + s->ring0) % N;
+        f.meta[t].in_off = f.uni_in0 + p * f.uni_in_rec;
+        f.meta[t].fac_off = p * f.uni_fac_rec;
+      }
+      HIP_TRY(hipMemcpyAsync(s->d_meta2, f.meta.data(), sizeof(gar_stage_meta) * f.meta.size(), hipMemcpyHostToDevice,
+                             s->stream));
+      HIP_TRY(hipMemset2DAsync(s->d_fac2 + f.meta[N - 1].fac_off, sizeof(double) * (size_t)f.fac_doubles, 0,
+                               sizeof(double) * (size_t)f.uni_fac_rec, (size_t)s->batch, s->stream));
+      s->fold_expanded = false;
+    }
     HIP_TRY(hipMemsetAsync(s->d_init, 0, sizeof(double) * (size_t)s->init_doubles * s->batch, s->stream));
     // the last-but-one factor is re-created (zero) like the reference's StageFactor (:84-85): one
     // strided memset over the batch, asynchronous

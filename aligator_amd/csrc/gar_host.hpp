@@ -127,6 +127,14 @@ struct KernelBinding {
   // hand-over knot per (problem, local leg)
   bool cseg_on = false;
   CsegKernels cseg;
+  // The serial twin of `fold` (GAR_HIP_SERIAL_FOLD=1; `fold` is set with it): a serial problem whose constrained knots
+  // all have D = 0, on the unconstrained serial family of its (nx, nu).  The family sweeps the folded buffers
+  // (flay, d_prob2, d_fac2) in its own record formats, kept in sf_*; the caller-facing buffers (d_prob, d_fac) are in
+  // the any-dimension format -- fb_t2 = vxx_packed = qr_packed = false -- which is what the any-dimension serial kernels
+  // read and write for the flagged problems and what gar_expand_serial writes for the others.
+  bool serial_fold = false;
+  bool serial_fold_fallback = false; // the any-dimension kernels fit a CU's LDS: they take the flagged problems
+  bool sf_fb_t2 = false, sf_vxx_packed = false, sf_qr_packed = false;
 };
 
 } // namespace

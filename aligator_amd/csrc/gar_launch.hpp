@@ -25,8 +25,17 @@ gar::MfmaParams make_mfma_scratch_params(gar_hip_solver *s, double mueq, double 
 }
 // parameters of the serial specialised sweeps (gar_backward_mfma, gar_backward_wave and its chain)
 gar::MfmaParams make_mfma_params(gar_hip_solver *s, double mueq) {
-  gar::MfmaParams M = make_mfma_scratch_params(s, mueq, s->d_fac, s->fac_doubles, s->uni_fac_rec,
-                                               s->meta[s->horizon].fac_off, status_flags(s));
+  // (a serial-fold solver: the family sweeps the folded knots into its own records; the flags belong to the fold)
+  const gar::HostLayout &L = s->serial_fold ? *s->flay : static_cast<const gar::HostLayout &>(*s);
+  gar::MfmaParams M = make_mfma_scratch_params(s, mueq, s->serial_fold ? s->d_fac2 : s->d_fac, L.fac_doubles, L.uni_fac_rec,
+                                               L.meta[s->horizon].fac_off, s->serial_fold ? nullptr : status_flags(s));
+  if (s->serial_fold) {
+    M.prob = s->d_prob2;
+    M.prob_stride = L.prob_doubles;
+    M.in_off0 = L.uni_in0;
+    M.in_rec = L.uni_in_rec;
+    M.in_offN = L.meta[s->horizon].in_off;
+  }
   M.trace = s->d_trace;
   M.init = s->wave_kernel && s->wave_fused_init ? s->d_init : nullptr;
   M.init_stride = s->init_doubles;
@@ -206,9 +215,26 @@ int backward_seg_legs(gar_hip_solver *s, double mueq, const LegChunk &c) {
 }
 
 // the serial specialised sweep (4-wave mfma kernel, or the one-wave kernel and its constrained chain), then the initial stage
+// the any-dimension kernels' view of a serial-fold solver's folded records: the stand-alone initial stage of the family
+gar::GenericParams make_folded_params(gar_hip_solver *s, double mueq) {
+  gar::GenericParams P = make_params(s, mueq);
+  P.meta = s->d_meta2;
+  P.fac = s->d_fac2;
+  P.fac_stride = s->flay->fac_doubles;
+  P.vxx_packed = s->sf_vxx_packed ? 1 : 0;
+  return P;
+}
+
 int backward_serial(gar_hip_solver *s, double mueq) {
   const gar::MfmaParams M = make_mfma_params(s, mueq);
+  const gar::GenericParams I = s->serial_fold ? make_folded_params(s, mueq) : make_params(s, mueq);
   HIP_TRY(stamp(s, 0));
+  if (s->serial_fold) { // knots with nc > 0: fold C, d into Q, q in the family's knot format; problems with D != 0 get flagged
+    s->fold_mueq = mueq;
+    s->fold_expanded = s->coupled_known = false;
+    hipLaunchKernelGGL(gar::gar_fold_serial, dim3((unsigned)(s->horizon + 1), (unsigned)s->batch), dim3(256),
+                       fold_lds_bytes(s), s->stream, make_serial_fold_params(s));
+  }
   if (s->wave_kernel) {
     const int wpb = s->waves_per_block;
     hipLaunchKernelGGL(s->wave_kernel, dim3((unsigned)((s->batch + wpb - 1) / wpb)),
@@ -230,10 +256,25 @@ int backward_serial(gar_hip_solver *s, double mueq) {
   } else if (s->n0 <= 128) { // one wave per problem (wave-scope Bunch-Kaufman handles n <= 128)
     hipLaunchKernelGGL(gar::gar_initial_wave, dim3((unsigned)s->batch), dim3(64),
                        (size_t)gar::gar_initial_wave_lds_doubles(s->n0, s->nth0) * sizeof(double),
-                       s->stream, make_params(s, mueq));
+                       s->stream, I);
   } else {
     hipLaunchKernelGGL(gar::gar_initial_generic, dim3((unsigned)s->batch), dim3(256),
-                       (size_t)s->lds.total * sizeof(double), s->stream, make_params(s, mueq));
+                       (size_t)s->lds.total * sizeof(double), s->stream, I);
+  }
+  if (s->serial_fold) {
+    // The flagged problems: the family has swept their folded records like everyone's (it has no per-problem skip, and
+    // none was added: its code is what it was) -- that result is never read.  Their status word is cleared and the
+    // any-dimension serial sweep, initial stage included, takes them from the caller's knots into the caller-visible
+    // records (every other problem: an early exit).  Where the any-dimension kernels do not fit a CU's LDS nobody can
+    // take them: reported as failed.
+    hipLaunchKernelGGL(gar::gar_fold_settle_flagged, dim3((unsigned)((s->batch + 255) / 256)), dim3(256), 0, s->stream,
+                       status_words(s), status_flags(s), s->batch, s->serial_fold_fallback ? 0 : 1);
+    if (s->serial_fold_fallback) {
+      gar::GenericParams G = make_params(s, mueq);
+      G.only = status_flags(s);
+      hipLaunchKernelGGL(gar::gar_backward_generic, dim3(1u, (unsigned)s->batch), dim3(GAR_BACKWARD_THREADS),
+                         (size_t)s->lds.total * sizeof(double), s->stream, G);
+    }
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(stamp(s, 2));
@@ -272,14 +313,15 @@ inline size_t lds_round(size_t b) { return (b + kLdsGranule - 1) / kLdsGranule *
 gar::MfmaFwdParams make_mfma_fwd_params(gar_hip_solver *s) {
   gar::MfmaFwdParams F{};
   const int N = s->horizon;
-  F.fac = s->d_fac;
+  const gar::HostLayout &L = s->serial_fold ? *s->flay : static_cast<const gar::HostLayout &>(*s); // (the family's own records)
+  F.fac = s->serial_fold ? s->d_fac2 : s->d_fac;
   F.init = s->d_init;
   F.sol = s->d_sol;
-  F.fac_stride = s->fac_doubles;
+  F.fac_stride = L.fac_doubles;
   F.init_stride = s->init_doubles;
   F.sol_stride = s->sol_doubles;
-  F.fac_rec = s->uni_fac_rec;
-  F.fac_offN = s->meta[N].fac_off;
+  F.fac_rec = L.uni_fac_rec;
+  F.fac_offN = L.meta[N].fac_off;
   F.horizon = N;
   F.nc0 = s->nc0;
   F.sol_u = (int)s->sol_u;
@@ -327,6 +369,16 @@ int forward_serial(gar_hip_solver *s) {
                        s->batch);
   } else {
     hipLaunchKernelGGL(s->mfma_fwd_kernel, dim3((unsigned)s->batch), dim3(64), s->mfma_fwd_lds_bytes, s->stream, F);
+  }
+  if (s->serial_fold) { // v_t = zff + Z x_t; the flagged problems: the any-dimension roll-out over the caller-visible records
+    hipLaunchKernelGGL(gar::gar_constraint_multipliers, dim3((unsigned)(s->horizon + 1), (unsigned)s->batch), dim3(64), 0,
+                       s->stream, make_fold_params(s));
+    if (s->serial_fold_fallback) {
+      gar::GenericParams G = make_params(s, 0.0);
+      G.only = status_flags(s);
+      hipLaunchKernelGGL(gar::gar_forward_generic, dim3(1u, (unsigned)s->batch), dim3(GAR_FORWARD_THREADS),
+                         (size_t)s->lds.ftotal * sizeof(double), s->stream, G);
+    }
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(stamp(s, 4));

@@ -199,6 +199,53 @@ void select_leg_kernel(gar_hip_solver *s) {
   s->fold = any_nc && s->leg_bwd_kernel != nullptr;
 }
 
+// GAR_HIP_SERIAL_FOLD=1: a serial problem of an exact kSpecialised shape with constraints on some (or all) knots, on
+// that shape's unconstrained serial family through the fold (gar_fold.hpp) -- the serial twin of select_leg_kernel's
+// `fold`.  The uniform kConstrained rows keep their own chain.  The fold kernel stages C and C / mu in its default
+// dynamic LDS.  The any-dimension kernels are the fallback for problems with D != 0; where they do not fit a CU's LDS
+// ((56, 24) with constraints: no solver at all without the switch) there is none, and such a problem is reported as a
+// failed stage (serial_fold_fallback, backward_serial).
+bool select_serial_fold(gar_hip_solver *s) {
+  const int N = s->horizon;
+  if (!option_is("GAR_HIP_SERIAL_FOLD", "1") || s->world != 1 || s->padded)
+    return false;
+  const int nx = s->meta[0].nx, nu = s->meta[0].nu;
+  int nc_max = 0;
+  bool uniform_nc = true;
+  for (int t = 0; t <= N; ++t) {
+    const gar_stage_meta &m = s->meta[t];
+    if (m.nx != nx || m.nu != (t < N ? nu : 0) || m.nx2 != nx || m.nth != 0)
+      return false;
+    nc_max = std::max(nc_max, (int)m.nc);
+    uniform_nc &= m.nc == s->meta[0].nc;
+  }
+  if (nc_max == 0 || sizeof(double) * (size_t)gar::fold_lds_doubles(nx, nc_max) > 48 * 1024)
+    return false;
+  if (!s->lds_error.empty() && s->n0 > 128) // (the stand-alone initial stage beyond one wave is the any-dimension kernels')
+    return false;
+  if (uniform_nc)
+    for (const CstrShape &sh : kConstrained)
+      if (sh.nx == nx && sh.nu == nu && sh.nc == nc_max)
+        return false;
+  for (const SpecShape &sh : kSpecialised)
+    if (sh.nx == nx && sh.nu == nu)
+      sh.bind_serial(s);
+  if (!(s->wave_kernel || s->mfma_kernel) || !s->mfma_fwd_kernel) { // (GAR_HIP_WIDE=generic-forward: no roll-out of the family's)
+    static_cast<gar::KernelBinding &>(*s) = gar::KernelBinding{};
+    s->init_closed = !option_is("GAR_HIP_INIT", "bk");
+    return false;
+  }
+  s->sf_fb_t2 = s->fb_t2;
+  s->sf_vxx_packed = s->fb_t2 || s->wide_vxx_packed;
+  s->sf_qr_packed = s->qr_packed;
+  s->fb_t2 = s->vxx_packed = s->qr_packed = false; // the caller-facing records: the any-dimension format
+  s->lean_fwd_kernel = nullptr;                     // the pipelined schedule is not offered (pipe_eligible)
+  s->wave_half_kernel = nullptr;
+  s->fold = s->serial_fold = true;
+  s->serial_fold_fallback = s->lds_error.empty();
+  return true;
+}
+
 void select_kernel(gar_hip_solver *s) {
   static_cast<gar::KernelBinding &>(*s) = gar::KernelBinding{}; // nothing of the family bound before survives
   s->init_closed = !option_is("GAR_HIP_INIT", "bk");
@@ -215,6 +262,8 @@ void select_kernel(gar_hip_solver *s) {
     return;
   }
   if (N < 1)
+    return;
+  if (!s->multi && select_serial_fold(s))
     return;
   const gar_stage_meta &m0 = s->meta[0];
   if (m0.nth != 0 || m0.nx2 != m0.nx)
@@ -372,7 +421,7 @@ int configure_padded_or_not(gar_hip_solver *s) {
     bool uniform_nc = nc > 0;
     for (int t = 0; t <= s->horizon; ++t)
       uniform_nc &= s->dims5[5 * (size_t)t + 2] == nc;
-    if (uniform_nc && !option_off("GAR_HIP_CSTR_SEG_LEGS") && gar::cseg_bind(nx, nu, nc, &s->cseg) &&
+    if (uniform_nc && !s->serial_fold && !option_off("GAR_HIP_CSTR_SEG_LEGS") && gar::cseg_bind(nx, nu, nc, &s->cseg) &&
         s->cseg.scratch_doubles(s->horizon, s->num_legs) <= s->flay->fac_doubles) {
       s->cseg_on = true;
       s->qr_packed = true; // the chain's kernels read only the lower triangles of Q and R (gar_layout.h); the fold unpacks
@@ -384,7 +433,8 @@ int configure_padded_or_not(gar_hip_solver *s) {
   s->any_nc = false;
   for (int t = 0; t <= s->horizon; ++t) {
     const int32_t *d = &s->dims5[5 * (size_t)t];
-    s->mu_divides |= d[2] > 0 && (d[1] == 0 || s->wave_kernel != nullptr);
+    // (a serial-fold solver divides like a leg-fold one: on the terminal knot outright, elsewhere on the fold's say-so)
+    s->mu_divides |= d[2] > 0 && (d[1] == 0 || (s->wave_kernel != nullptr && !s->serial_fold));
     s->any_nc |= d[2] > 0;
   }
   return GAR_HIP_OK;

@@ -192,6 +192,8 @@ class BatchedRiccatiSolver:
             self._check(L.gar_hip_packed_stage_dims(h, t, pd[t].ctypes.data_as(C.POINTER(C.c_int32))))
         self.packed_dims = pd
         self.qr_packed = bool(self.record_format & 1)
+        # GAR_HIP_SERIAL_FOLD=1 bound: constrained knots with D = 0 folded onto the unconstrained serial family
+        self.serial_fold = self.num_legs == 1 and self.kernel_name.endswith("+fold")
         self._factors_cache = {}
         self._mueq = None   # of the last backward (datas[t].kktMat is formed on request)
 

@@ -234,6 +234,9 @@ int gar_hip_packed_stage_dims(const gar_hip_solver *s, int t, int32_t out[5]);
 #define GAR_HIP_FMT_QR_PACKED 1
 #define GAR_HIP_FMT_VXX_PACKED 2
 #define GAR_HIP_FMT_FB_T2 4
+/* A serial-fold solver (switch SERIAL_FOLD) reports NO packed flag: these calls describe the caller-facing records
+ * (gar_hip_device_problems / gar_hip_device_factors: full blocks, row-major fb, full Vxx, the knots' own nc), not the
+ * folded records its kernel family sweeps, which stay inside the library. */
 int gar_hip_device_stage_layout(const gar_hip_solver *s, int t, int64_t out[11]);
 int gar_hip_device_sizes(const gar_hip_solver *s, int64_t out[8]);
 int gar_hip_device_record_format(const gar_hip_solver *s);
@@ -269,7 +272,8 @@ int gar_hip_update_lq_subproblem_device(gar_hip_solver *s, const double *deriv_d
  * constrained segment legs, which bind only where the terminal knot is constrained -- is GAR_HIP_ERR_FACTOR before
  * anything is launched (the reference: infinities).  On the other leg-mode solvers with constrained knots the device
  * hands such a problem to the generic leg kernels, which solve it where [Rhat D^T; D 0] is nonsingular and report the
- * singular stages (the reference's "failed stage" exception, e.g. on [Rhat 0; 0 0] where D = 0) per problem.  A
+ * singular stages (the reference's "failed stage" exception, e.g. on [Rhat 0; 0 0] where D = 0) per problem; a
+ * serial-fold solver (switch SERIAL_FOLD) does the same with the any-dimension serial kernels.  A
  * non-finite mueq on a problem with constrained knots is GAR_HIP_ERR_FACTOR up front on every family. */
 int gar_hip_backward(gar_hip_solver *s, double mueq);
 int gar_hip_backward_async(gar_hip_solver *s, double mueq);
@@ -419,6 +423,15 @@ int gar_hip_debug_trace(gar_hip_solver *s, int enable, long long out[64]);
  *                                  acceptance of an unpivoted positive definite R-hat (deviation 7)
  *   LEGS = generic | LEG_WAVES = 1 | SEG_LEGS = 0 | FOLD = 0     leg mode: the any-dimension leg kernels / one wave
  *                                  per leg / no segment legs on the wide shape / constrained knots not folded
+ *   SERIAL_FOLD = 1                serial in time (num_legs = 1), opt-in: a problem of an exact specialised (nx, nu) --
+ *                                  (36,12), (32,12), (16,8), (12,8), (12,4), (8,4), (56,24) -- with constraints on some
+ *                                  or all knots runs on that shape's unconstrained family (wave<> / mfma<> / pair<>,
+ *                                  kernel name "<family>+fold") where its constrained knots have D = 0: Q += C^T C / mu,
+ *                                  q += C^T d / mu (csrc/gar_fold.hpp; a terminal goal constraint is the common case).
+ *                                  A problem with some D != 0 is taken by the any-dimension kernels inside the same
+ *                                  calls (where those do not fit a CU's LDS -- (56,24) with constraints -- it is
+ *                                  reported as a failed stage).  The uniform constrained shapes (36,12,32), (16,8,8),
+ *                                  (8,4,4) keep their own family.  No pipelined schedule.  Default off: "generic"
  *   CSTR_SEG_LEGS = 0              leg mode, problems with D != 0 on the any-dimension leg kernels instead of the
  *                                  constrained segment legs (csrc/gar_cstr_seg.hpp; (36,12,32), (16,8,8), (8,4,4));
  *                                  CSTR_SEG_LEG_END = 0 (per launch): their leg ends through the stage chain (two rounds)
@@ -444,7 +457,7 @@ const char *gar_hip_get_option(const char *name);
  * first orders the solver's stream behind the half streams, so code that touches the records only through
  * this header needs no change; a caller that enqueues its own kernels on the records calls gar_hip_sync (or any
  * getter) first.  halves = 0 / 1: off.  GAR_HIP_ERR_UNSUPPORTED unless the solver runs the serial
- * one-wave-per-problem family (batch > number of CUs, nc = nth = 0, at least 2 problems).
+ * one-wave-per-problem family (batch > number of CUs, nc = nth = 0, at least 2 problems; a serial-fold solver does not).
  * halves = -1: the LIBRARY chooses (never an error) -- two halves iff the solver is eligible and each half fills every
  * SIMD of the device with a backward wave (batch >= 8 x #CUs: 2 048 on an MI355X), plain otherwise.  This is what a
  * new solver starts with (round 6; switch PIPELINE above), and what a cycleAppend that rebuilds the solver for other
