@@ -27,12 +27,12 @@ static int upload_stage_impl(gar_hip_solver *s, int b, int t, const double *Q, c
   const int nx = s->unx, nu = m.nu > 0 ? s->unu : 0, NX = m.nx, NU = m.nu;
   if (!Q || !q || !A || !f || (nu > 0 && (!S || !R || !r || !B)))
     return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_stage: null block");
-  if (s->staged) {
+  if (s->buf.staged) {
     // straight into the pinned staging record, one pass: real rows / columns copied column by column, the dummy
     // ones written beside them (no intermediate padded copy of the blocks); then the knot is one dirty range
     const gar_knot_offsets o = gar_knot_layout(NX, NU, 0, NX, 0);
-    double *rec = s->h_prob + (int64_t)b * s->prob_doubles + m.in_off;
-    const bool nt = s->stage_nt;
+    double *rec = s->buf.h_prob + (int64_t)b * s->prob_doubles + m.in_off;
+    const bool nt = s->buf.stage_nt;
     auto put = [rec, nt](int64_t off, const double *src, int r, int c, int R, int C, double diag) {
       double *dst = rec + off;
       if (r == R) { // same column pitch (e.g. (56, 22) -> (56, 24): only controls are added): the real columns in one go
@@ -132,7 +132,7 @@ int gar_hip_condensed_resolved(gar_hip_solver *s, int b, int *out) {
   GAR_MULTI(s, gar_hip_condensed_resolved(s->multi->subs[0], b, out));
   if (s->num_legs < 2 || !out)
     return fail(GAR_HIP_ERR_ARG, "condensed info needs leg mode");
-  const double *info = s->d_cscratch + (int64_t)b * s->cscratch_doubles + cond_info_off(s);
+  const double *info = s->buf.d_cscratch + (int64_t)b * s->cscratch_doubles + cond_info_off(s);
   double v = 0.0;
   if (int rc = d2h(s, &v, info + 3, 1))
     return rc;
@@ -148,7 +148,7 @@ int gar_hip_condensed_backward_error(gar_hip_solver *s, int b, double *out) {
   GAR_MULTI(s, gar_hip_condensed_backward_error(s->multi->subs[0], b, out));
   if (s->num_legs < 2 || !out)
     return fail(GAR_HIP_ERR_ARG, "condensed info needs leg mode");
-  const double *info = s->d_cscratch + (int64_t)b * s->cscratch_doubles + cond_info_off(s);
+  const double *info = s->buf.d_cscratch + (int64_t)b * s->cscratch_doubles + cond_info_off(s);
   double v[3] = {0.0, 0.0, 0.0};
   if (int rc = d2h(s, v, info, 3))
     return rc;
@@ -165,7 +165,7 @@ int gar_hip_get_solution(gar_hip_solver *s, int b, double *xs, double *us, doubl
   if (!s->padded)
     return get_solution_dev(s, b, xs, us, vs, lbdas);
   std::vector<double> rec((size_t)s->sol_doubles);
-  HIP_TRY(hipMemcpyAsync(rec.data(), s->d_sol + (int64_t)b * s->sol_doubles, sizeof(double) * rec.size(),
+  HIP_TRY(hipMemcpyAsync(rec.data(), s->buf.d_sol + (int64_t)b * s->sol_doubles, sizeof(double) * rec.size(),
                          hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   strip_solution(s, rec.data(), xs, us, vs, lbdas);

@@ -65,20 +65,6 @@ int fail(int code, const std::string &msg) {
 
 inline int align2(int x) { return (x + 1) & ~1; }
 
-// Every device / pinned-host allocation of the library goes through these two and is counted
-// (gar_hip_debug_alloc_count): the reference runs backward / forward under ALIGATOR_NOMALLOC_SCOPED
-// (gar/proximal-riccati.hxx:35, tests/nomalloc.cpp); tests/test_nomalloc.py asserts the same here -- the count
-// does not move across repeated backward + forward calls.
-std::atomic<long long> g_alloc_count{0};
-inline hipError_t gar_dev_malloc(void **p, size_t bytes) {
-  g_alloc_count.fetch_add(1, std::memory_order_relaxed);
-  return hipMalloc(p, bytes);
-}
-inline hipError_t gar_host_malloc(void **p, size_t bytes, unsigned flags) {
-  g_alloc_count.fetch_add(1, std::memory_order_relaxed);
-  return hipHostMalloc(p, bytes, flags);
-}
-
 // Tracing hooks (the reference brackets the same places with Tracy zones: backwardImpl
 // riccati-kernel.hxx:108, "factor_initial" proximal-riccati.hxx:43, forwardImpl riccati-kernel.hxx:320,
 // "parallel_backward" / "parallel_forward" parallel-solver.hxx:134,213, assembleCondensedSystem :87):
@@ -174,26 +160,12 @@ struct gar_hip_solver : gar::HostLayout, gar::KernelBinding {
   // `flay` = the layout of the folded problem (KernelBinding::fold: same knots, nc = 0) or of the segment legs'
   // scratch records (seg_bwd_kernel: same knots, serial); d_prob2 / d_fac2 / d_meta2 its device records
   std::unique_ptr<gar::HostLayout> flay;
-  bool fold_expanded = false, coupled_known = false;
   bool mu_divides = false; // some knot's solve divides by mueq outright (see gar_hip_backward_legs_async)
   bool any_nc = false;     // some knot carries constraints: a non-finite mueq is refused (ibid.)
-  int *d_cseg_resume = nullptr;
-  double *d_prob2 = nullptr, *d_fac2 = nullptr;
-  gar_stage_meta *d_meta2 = nullptr;
   double fold_mueq = 0.0;
-  std::vector<int> h_coupled;
-  gar_stage_meta *d_meta = nullptr;
-  double *d_prob = nullptr, *d_fac = nullptr, *d_sol = nullptr, *d_init = nullptr;
-  double *d_theta = nullptr;
-  int *d_status = nullptr;
-  double *d_kkt = nullptr; // gar_hip_get_kkt's staging ((nu+nc)^2 doubles, allocated on first use)
-  int64_t kkt_doubles = 0;
   // leg mode
   int nxb = 0;
   int64_t tuple_doubles = 0, cscratch_doubles = 0;
-  double *d_bound_local = nullptr, *d_bound_all = nullptr, *d_csol = nullptr,
-         *d_cscratch = nullptr;
-  bool bound_all_owned = false;
   int legs_per_rank = 0;
   double cond_threshold = 1e-10; // parallel-solver.hpp:92
   double cond_backward_ok = GAR_CONDENSED_BACKWARD_OK; // gar_hip_set_condensed_backward_ok
@@ -201,52 +173,22 @@ struct gar_hip_solver : gar::HostLayout, gar::KernelBinding {
   bool cond_cr = false;      // ... and the J remaining blocks by block cyclic reduction, a workgroup per block and level
                              // (gar_condensed_cr.hpp; GAR_HIP_CONDENSED_CR=0: the one-workgroup chain, =<k>: from k legs on)
   int max_refinement = 5;        // parallel-solver.hpp:94
-  // host staging
-  double *h_prob = nullptr; // pinned, batch * prob_doubles (when small enough)
-  bool staged = false, dirty = false;
-  bool stage_nt = false; // pack with non-temporal stores (problems of >= 12 MiB; GAR_HIP_STAGE_NT=0/1 overrides)
-  // what the host wrote into the staging area since the last flush: per problem, a sorted list of
-  // disjoint [lo, hi) ranges (doubles).  commit() copies exactly these, so knots a device-resident
-  // producer wrote in place (gar_hip_device_problems) survive a later set_init / upload_stage
-  std::vector<std::vector<std::pair<int64_t, int64_t>>> dirty_iv;
-  hipStream_t own_stream = nullptr, stream = nullptr;
+  // run state (gar_host.hpp): what dies with the layout, and what is created on first use and dies with the solver
+  gar::LayoutState buf;
+  gar::PipeState pipe;
+  gar::LazyState lazy;
+  Stream own_stream;            // created with the solver; `stream` is it or the caller's (gar_hip_set_stream)
+  hipStream_t stream = nullptr;
   gar::LdsPlan lds{};
   gar::DensePlan dense_lds{};
   int last_failed = 0;
   std::string lds_error;   // the generic kernels do not fit a CU's LDS (fatal unless a specialised family serves the shape)
-  long long *d_trace = nullptr; // 64 cycle stamps (debug)
-  long long *d_deriv_off = nullptr; // device-resident updateLQSubproblem: HostLayout::deriv_off on the device
-  // bulk read-back (gar_hip_fetch_results): HostLayout::gain_off on the device, the device gather buffer and the
-  // pinned host buffer [solution | ff_all | fb_all] of one problem
-  long long *d_gain_off = nullptr;
-  double *d_gains = nullptr, *h_results = nullptr;
-  // optional per-kernel timing of the sweep (bench.py's roofline figure): HIP events recorded on
-  // the launch stream around the backward sweep kernel, the initial-stage kernel and the forward
-  // sweep kernel of the LAST backward/forward calls
-  bool timing = false;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  // gar_hip_prefetch_gains: the bulk read-back of the gains started right behind the backward sweep on a second
-  // stream, so that it overlaps the forward sweep and the solution read-back
-  hipStream_t aux_stream = nullptr;
-  hipEvent_t ev_main = nullptr, ev_pref = nullptr;
-  int pref_b = -1;             // problem whose gains are in flight / in h_results (-1: none)
-  // gar_hip_backward_blocks on a problem without parameter: the roll-out and the solution's copy are enqueued BEHIND the
-  // sweep before the host waits for the status word, so that gar_hip_forward / the solution fetch find them done
-  int *h_status = nullptr;     // pinned
-  hipEvent_t ev_status = nullptr, ev_sol = nullptr;
+  bool timing = false;         // gar_hip_set_timing (LazyState::ev)
+  int pref_b = -1;             // gar_hip_prefetch_gains: problem whose gains are in flight / in h_results (-1: none)
   bool eager_fwd = false;      // d_sol and h_results hold the roll-out of the last sweep (theta = none)
   bool pref_collapsed = false; // collapseFeedback ran since: stage 0's gains are fetched again
-  // ---- pipelined sweep (gar_hip_set_pipeline; the serial one-wave family, batch >= 2) --------------------------
-  // The batch is cut in two halves with a stream each; backward sweeps alternate between the halves (events), the
-  // forward sweep of a half is gar_forward_lean, which fits in the registers and the LDS the backward wave of the
-  // OTHER half leaves free on every SIMD (gar_forward_lean.hpp): B(h0) | F(h0) + B(h1) | F(h1) + B'(h0) | ...
-  int pipe_halves = 0;                 // 0: off
-  int pipe_requested = 0;              // what the caller last asked gar_hip_set_pipeline for (a rebuild re-validates it)
-  hipStream_t pipe_stream[2] = {nullptr, nullptr};
-  hipEvent_t pipe_evB[2] = {nullptr, nullptr}, pipe_evF[2] = {nullptr, nullptr}, pipe_evFork = nullptr;
-  hipEvent_t pipe_evT[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}}; // timing
-  bool pipe_evB_valid[2] = {false, false};
-  bool pipe_forked = false;            // the half streams hold work the caller's stream has not been ordered behind
+  int pipe_halves = 0;         // the pipelined sweep (PipeState), 0: off
+  int pipe_requested = 0;      // what the caller last asked gar_hip_set_pipeline for (a rebuild re-validates it)
   // SolverProxDDP builds the terminal knot with nx2 = 0 (solvers/proxddp/workspace.hxx:54-55); nothing of the
   // algorithm reads a terminal knot's A, f (riccati-kernel.hxx:130-193).  Such a knot is taken in as nx2 = nx -- the
   // uniform record every kernel family addresses -- with zeros for the two blocks; the gains of that knot go back
@@ -262,9 +204,9 @@ namespace {
 //   [batch, batch + 4)              status_counters: MfmaParams::slow -- slow-path stages (2), constrained stages (2)
 //   [batch + 4, 2 batch + 4)        status_flags: a word per problem -- MfmaParams::resume; folded solvers: "flagged, D != 0"
 constexpr int kStatusCounters = 4;
-inline int *status_words(const gar_hip_solver *s, int b0 = 0) { return s->d_status + b0; }
-inline int *status_counters(const gar_hip_solver *s) { return s->d_status + s->batch; }
-inline int *status_flags(const gar_hip_solver *s) { return s->d_status + s->batch + kStatusCounters; }
+inline int *status_words(const gar_hip_solver *s, int b0 = 0) { return s->buf.d_status + b0; }
+inline int *status_counters(const gar_hip_solver *s) { return s->buf.d_status + s->batch; }
+inline int *status_flags(const gar_hip_solver *s) { return s->buf.d_status + s->batch + kStatusCounters; }
 inline size_t status_bytes(size_t b, bool flags) { return sizeof(int) * (b + kStatusCounters + (flags ? b : 0)); }
 
 // ---- layout ---------------------------------------------------------------
@@ -504,14 +446,14 @@ replan:
 
 gar::GenericParams make_params(gar_hip_solver *s, double mueq) {
   gar::GenericParams P{};
-  P.meta = s->d_meta;
-  P.prob = s->d_prob;
-  P.fac = s->d_fac;
-  P.sol = s->d_sol;
-  P.init = s->d_init;
-  P.status = s->d_status;
-  P.boundary = s->d_bound_local;
-  P.csol = s->d_csol;
+  P.meta = s->buf.d_meta;
+  P.prob = s->buf.d_prob;
+  P.fac = s->buf.d_fac;
+  P.sol = s->buf.d_sol;
+  P.init = s->buf.d_init;
+  P.status = s->buf.d_status;
+  P.boundary = s->buf.d_bound_local;
+  P.csol = s->buf.d_csol;
   P.theta = nullptr;
   P.prob_stride = s->prob_doubles;
   P.fac_stride = s->fac_doubles;
@@ -545,7 +487,7 @@ inline void stage_fence() {
 }
 
 void mark_dirty(gar_hip_solver *s, int b, int64_t lo, int64_t hi) {
-  auto &iv = s->dirty_iv[(size_t)b];
+  auto &iv = s->buf.dirty_iv[(size_t)b];
   // the common pattern is "append right after the last range" (knot after knot): O(1); gaps of
   // one double are record-alignment padding and merge as well
   if (!iv.empty() && lo >= iv.back().first && lo <= iv.back().second + 1) {
@@ -564,18 +506,18 @@ void mark_dirty(gar_hip_solver *s, int b, int64_t lo, int64_t hi) {
       iv.resize(w + 1);
     }
   }
-  s->dirty = true;
+  s->buf.dirty = true;
 }
 
 int commit(gar_hip_solver *s) {
-  if (!(s->staged && s->dirty))
+  if (!(s->buf.staged && s->buf.dirty))
     return GAR_HIP_OK;
   stage_fence();
   const int64_t P = s->prob_doubles;
   // whole problems, back to back: one copy per run of fully rewritten problems
   int b = 0;
   while (b < s->batch) {
-    auto &iv = s->dirty_iv[(size_t)b];
+    auto &iv = s->buf.dirty_iv[(size_t)b];
     if (iv.empty()) {
       ++b;
       continue;
@@ -583,27 +525,27 @@ int commit(gar_hip_solver *s) {
     const bool whole = iv.size() == 1 && iv[0].first == 0 && iv[0].second >= P - 1;
     if (whole) {
       int e = b + 1;
-      while (e < s->batch && s->dirty_iv[(size_t)e].size() == 1 && s->dirty_iv[(size_t)e][0].first == 0 &&
-             s->dirty_iv[(size_t)e][0].second >= P - 1)
+      while (e < s->batch && s->buf.dirty_iv[(size_t)e].size() == 1 && s->buf.dirty_iv[(size_t)e][0].first == 0 &&
+             s->buf.dirty_iv[(size_t)e][0].second >= P - 1)
         ++e;
-      HIP_TRY(hipMemcpyAsync(s->d_prob + (int64_t)b * P, s->h_prob + (int64_t)b * P,
+      HIP_TRY(hipMemcpyAsync(s->buf.d_prob + (int64_t)b * P, s->buf.h_prob + (int64_t)b * P,
                              sizeof(double) * (size_t)P * (size_t)(e - b), hipMemcpyHostToDevice,
                              s->stream));
       for (int k = b; k < e; ++k)
-        s->dirty_iv[(size_t)k].clear();
+        s->buf.dirty_iv[(size_t)k].clear();
       b = e;
       continue;
     }
     for (const auto &r : iv) {
       const int64_t hi = std::min(r.second, P);
-      HIP_TRY(hipMemcpyAsync(s->d_prob + (int64_t)b * P + r.first, s->h_prob + (int64_t)b * P + r.first,
+      HIP_TRY(hipMemcpyAsync(s->buf.d_prob + (int64_t)b * P + r.first, s->buf.h_prob + (int64_t)b * P + r.first,
                              sizeof(double) * (size_t)(hi - r.first), hipMemcpyHostToDevice,
                              s->stream));
     }
     iv.clear();
     ++b;
   }
-  s->dirty = false;
+  s->buf.dirty = false;
   return GAR_HIP_OK;
 }
 
@@ -657,12 +599,12 @@ inline void pack_lower(double *dst, const double *src, int r, int R, double diag
 // (asynchronously, pinned -> HBM) while the caller packs the next knots -- one Newton
 // iteration's 7.6 MB of knots then costs max(host packing, PCIe), not their sum
 int flush_if_grown(gar_hip_solver *s, int b) {
-  auto &iv = s->dirty_iv[(size_t)b];
+  auto &iv = s->buf.dirty_iv[(size_t)b];
   if (!iv.empty() && iv.back().second - iv.back().first >= (int64_t)(1 << 17)) {
     stage_fence();
     const int64_t lo = iv.back().first, hi = std::min(iv.back().second, s->prob_doubles);
-    HIP_TRY(hipMemcpyAsync(s->d_prob + (int64_t)b * s->prob_doubles + lo,
-                           s->h_prob + (int64_t)b * s->prob_doubles + lo,
+    HIP_TRY(hipMemcpyAsync(s->buf.d_prob + (int64_t)b * s->prob_doubles + lo,
+                           s->buf.h_prob + (int64_t)b * s->prob_doubles + lo,
                            sizeof(double) * (size_t)(hi - lo), hipMemcpyHostToDevice, s->stream));
     iv.pop_back();
   }
@@ -672,16 +614,16 @@ int flush_if_grown(gar_hip_solver *s, int b) {
 int write_block(gar_hip_solver *s, int b, int64_t off, const double *src, int64_t n) {
   if (n <= 0)
     return GAR_HIP_OK;
-  if (s->staged) {
-    double *dst = s->h_prob + (int64_t)b * s->prob_doubles + off;
+  if (s->buf.staged) {
+    double *dst = s->buf.h_prob + (int64_t)b * s->prob_doubles + off;
     if (src)
-      stage_copy(dst, src, (size_t)n, s->stage_nt);
+      stage_copy(dst, src, (size_t)n, s->buf.stage_nt);
     else
       std::memset(dst, 0, sizeof(double) * (size_t)n);
     mark_dirty(s, b, off, off + n);
     return flush_if_grown(s, b);
   }
-  double *dst = s->d_prob + (int64_t)b * s->prob_doubles + off;
+  double *dst = s->buf.d_prob + (int64_t)b * s->prob_doubles + off;
   if (src)
     HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s->stream));
   else
@@ -714,23 +656,23 @@ gar::LegParams make_leg_params(gar_hip_solver *s) {
   gar::LegParams Q{};
   // folded solvers: the wave-leg family sweeps the folded knots and keeps its own (nc = 0) factor records; problems
   // with D != 0 are skipped (the generic leg kernels or the constrained segment legs take them)
-  Q.M = s->fold ? mfma_common(s, *s->flay, s->d_prob2, s->d_fac2, s->flay->fac_doubles)
-                : mfma_common(s, *s, s->d_prob, s->d_fac, s->fac_doubles);
-  Q.M.trace = s->d_trace;
-  Q.meta = s->fold ? s->d_meta2 : s->d_meta;
+  Q.M = s->fold ? mfma_common(s, *s->flay, s->buf.d_prob2, s->buf.d_fac2, s->flay->fac_doubles)
+                : mfma_common(s, *s, s->buf.d_prob, s->buf.d_fac, s->fac_doubles);
+  Q.M.trace = s->buf.d_trace;
+  Q.meta = s->fold ? s->buf.d_meta2 : s->buf.d_meta;
   Q.skip = s->fold ? status_flags(s) : nullptr;
   Q.num_legs = s->num_legs;
   Q.leg_begin = s->leg_begin;
-  Q.csol = s->d_csol;
-  Q.sol = s->d_sol;
+  Q.csol = s->buf.d_csol;
+  Q.sol = s->buf.d_sol;
   Q.sol_stride = s->sol_doubles;
   Q.sol_u = (int)s->sol_u;
   Q.sol_l = (int)s->sol_l;
   Q.nc0 = s->nc0;
-  Q.boundary = s->d_bound_local;
+  Q.boundary = s->buf.d_bound_local;
   Q.boundary_stride = (long long)s->legs_per_rank * s->tuple_doubles;
   Q.tuple_doubles = (int)s->tuple_doubles;
-  Q.cinfo = s->d_cscratch ? s->d_cscratch + cond_info_off(s) : nullptr;
+  Q.cinfo = s->buf.d_cscratch ? s->buf.d_cscratch + cond_info_off(s) : nullptr;
   Q.cinfo_stride = s->cscratch_doubles;
   return Q;
 }
@@ -746,13 +688,13 @@ size_t fold_lds_bytes(const gar_hip_solver *s) {
 gar::FoldParams make_fold_params(gar_hip_solver *s) {
   gar::FoldParams F{};
   const gar::HostLayout &f = *s->flay;
-  F.meta = s->d_meta;
-  F.meta2 = s->d_meta2;
-  F.prob = s->d_prob;
-  F.prob2 = s->d_prob2;
-  F.fac = s->d_fac;
-  F.fac2 = s->d_fac2;
-  F.sol = s->d_sol;
+  F.meta = s->buf.d_meta;
+  F.meta2 = s->buf.d_meta2;
+  F.prob = s->buf.d_prob;
+  F.prob2 = s->buf.d_prob2;
+  F.fac = s->buf.d_fac;
+  F.fac2 = s->buf.d_fac2;
+  F.sol = s->buf.d_sol;
   F.prob_stride = s->prob_doubles;
   F.prob2_stride = f.prob_doubles;
   F.fac_stride = s->fac_doubles;
@@ -788,114 +730,59 @@ gar::SerialFoldParams make_serial_fold_params(gar_hip_solver *s) {
 int ensure_expanded(gar_hip_solver *s) {
   if (!s->fold)
     return GAR_HIP_OK;
-  if (!s->fold_expanded) {
+  if (!s->buf.fold_expanded) {
     const dim3 grid((unsigned)(s->horizon + 1), (unsigned)s->batch);
     if (s->serial_fold)
       hipLaunchKernelGGL(gar::gar_expand_serial, grid, dim3(256), 0, s->stream, make_serial_fold_params(s));
     else
       hipLaunchKernelGGL(gar::gar_expand_constrained, grid, dim3(256), 0, s->stream, make_fold_params(s));
     HIP_TRY(hipGetLastError());
-    s->fold_expanded = true;
+    s->buf.fold_expanded = true;
   }
-  if (!s->coupled_known) {
-    s->h_coupled.assign((size_t)s->batch, 0);
-    HIP_TRY(hipMemcpyAsync(s->h_coupled.data(), status_flags(s), sizeof(int) * (size_t)s->batch,
+  if (!s->buf.coupled_known) {
+    s->buf.h_coupled.assign((size_t)s->batch, 0);
+    HIP_TRY(hipMemcpyAsync(s->buf.h_coupled.data(), status_flags(s), sizeof(int) * (size_t)s->batch,
                            hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    s->coupled_known = true;
+    s->buf.coupled_known = true;
   }
   return GAR_HIP_OK;
 }
 // fb / fth of problem b in the fbT2 device order?
 inline bool records_t2(const gar_hip_solver *s, int b) {
-  return s->fb_t2 && !(s->fold && s->coupled_known && s->h_coupled[(size_t)b] != 0);
+  return s->fb_t2 && !(s->fold && s->buf.coupled_known && s->buf.h_coupled[(size_t)b] != 0);
 }
 
 #include "gar_launch.hpp"
 
-void free_device(gar_hip_solver *s) {
-  (void)hipFree(s->d_meta);
-  (void)hipFree(s->d_prob);
-  (void)hipFree(s->d_fac);
-  (void)hipFree(s->d_sol);
-  (void)hipFree(s->d_init);
-  (void)hipFree(s->d_theta);
-  (void)hipFree(s->d_status);
-  if (s->d_kkt)
-    (void)hipFree(s->d_kkt);
-  s->d_kkt = nullptr;
-  s->kkt_doubles = 0;
-  (void)hipFree(s->d_bound_local);
-  if (s->bound_all_owned)
-    (void)hipFree(s->d_bound_all);
-  (void)hipFree(s->d_csol);
-  (void)hipFree(s->d_cscratch);
-
-  (void)hipFree(s->d_prob2);
-  (void)hipFree(s->d_fac2);
-  (void)hipFree(s->d_cseg_resume);
-  s->d_cseg_resume = nullptr;
-  (void)hipFree(s->d_meta2);
-  s->d_prob2 = s->d_fac2 = nullptr;
-  s->d_meta2 = nullptr;
-  (void)hipFree(s->d_trace);
-  s->d_trace = nullptr;
-  (void)hipFree(s->d_deriv_off);
-  s->d_deriv_off = nullptr;
-  (void)hipFree(s->d_gain_off);
-  (void)hipFree(s->d_gains);
-  if (s->h_results)
-    (void)hipHostFree(s->h_results);
-  s->d_gain_off = nullptr;
-  s->d_gains = nullptr;
-  s->h_results = nullptr;
-  if (s->h_prob)
-    (void)hipHostFree(s->h_prob);
-  s->d_meta = nullptr;
-  s->d_prob = s->d_fac = s->d_sol = s->d_init = s->d_theta = nullptr;
-  s->d_status = nullptr;
-  s->d_bound_local = s->d_bound_all = s->d_csol = s->d_cscratch = nullptr;
-  s->h_prob = nullptr;
-}
-
-// the two idioms of allocate(): a zeroed device buffer; a kernel's opt-in to `doubles` of dynamic LDS (> 64 KiB needs it)
-template <class T> hipError_t dev_zalloc(T **p, size_t bytes) {
-  const hipError_t e = gar_dev_malloc((void **)p, bytes);
-  return e != hipSuccess ? e : hipMemset(*p, 0, bytes);
-}
+// a kernel's opt-in to `doubles` of dynamic LDS (> 64 KiB needs it)
 template <class K> hipError_t max_lds(K kernel, size_t doubles) {
   return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(doubles * sizeof(double)));
 }
 
 int allocate(gar_hip_solver *s) {
   const size_t B = (size_t)s->batch;
-  HIP_TRY(gar_dev_malloc((void **)&s->d_meta, sizeof(gar_stage_meta) * s->meta.size()));
-  HIP_TRY(hipMemcpy(s->d_meta, s->meta.data(), sizeof(gar_stage_meta) * s->meta.size(),
+  HIP_TRY(s->buf.d_meta.alloc(s->meta.size()));
+  HIP_TRY(hipMemcpy(s->buf.d_meta, s->meta.data(), sizeof(gar_stage_meta) * s->meta.size(),
                     hipMemcpyHostToDevice));
-  HIP_TRY(dev_zalloc(&s->d_prob, sizeof(double) * (size_t)s->prob_doubles * B));
-  HIP_TRY(dev_zalloc(&s->d_fac, sizeof(double) * (size_t)s->fac_doubles * B));
-  HIP_TRY(dev_zalloc(&s->d_sol, sizeof(double) * (size_t)s->sol_doubles * B));
-  HIP_TRY(dev_zalloc(&s->d_init, sizeof(double) * (size_t)s->init_doubles * B));
-  HIP_TRY(gar_dev_malloc((void **)&s->d_theta, sizeof(double) * (size_t)std::max(s->nth0, 1) * B));
-  HIP_TRY(dev_zalloc(&s->d_status, status_bytes(B, true))); // (the three regions: status_words)
+  HIP_TRY(s->buf.d_prob.zalloc((size_t)s->prob_doubles * B));
+  HIP_TRY(s->buf.d_fac.zalloc((size_t)s->fac_doubles * B));
+  HIP_TRY(s->buf.d_sol.zalloc((size_t)s->sol_doubles * B));
+  HIP_TRY(s->buf.d_init.zalloc((size_t)s->init_doubles * B));
+  HIP_TRY(s->buf.d_theta.alloc((size_t)std::max(s->nth0, 1) * B));
+  HIP_TRY(s->buf.d_status.zalloc(status_bytes(B, true) / sizeof(int))); // (the three regions: status_words)
   if (s->num_legs > 1) {
     const int chunk = s->legs_per_rank; // >= this rank's own leg count; equal-sized chunks for the all-gather
     const int nblk = 2 * s->num_legs;
     const size_t bs = (size_t)s->nxb * s->nxb;
-    HIP_TRY(dev_zalloc(&s->d_bound_local, sizeof(double) * s->tuple_doubles * chunk * B));
-    if (s->world == 1) {
-      s->d_bound_all = s->d_bound_local;
-      s->bound_all_owned = false;
-    } else {
-      HIP_TRY(gar_dev_malloc((void **)&s->d_bound_all,
-                        sizeof(double) * s->tuple_doubles * chunk * s->world * B));
-      s->bound_all_owned = true;
-    }
-    HIP_TRY(gar_dev_malloc((void **)&s->d_csol, sizeof(double) * (size_t)nblk * s->nxb * B));
+    HIP_TRY(s->buf.d_bound_local.zalloc((size_t)s->tuple_doubles * chunk * B));
+    if (s->world > 1) // (one rank: the local buffer is the gathered one, LayoutState::bound_all)
+      HIP_TRY(s->buf.d_bound_gathered.alloc((size_t)s->tuple_doubles * chunk * s->world * B));
+    HIP_TRY(s->buf.d_csol.alloc((size_t)nblk * s->nxb * B));
     s->cscratch_doubles = cond_info_off(s) + 4;
     // (the info slots behind the blocks -- residual, steps, scale, resolved -- are read by the gar_hip_condensed_*
     // getters: defined before the first solve)
-    HIP_TRY(dev_zalloc(&s->d_cscratch, sizeof(double) * (size_t)s->cscratch_doubles * B));
+    HIP_TRY(s->buf.d_cscratch.zalloc((size_t)s->cscratch_doubles * B));
     s->cond_lds_doubles = (int)(3 * bs + 4 * s->nxb + 2 + (s->nxb + 16) / 2 + 2 + (s->nxb < 9 ? 9 * s->nxb : 0));
     {
       s->cond_reduced = !option_off("GAR_HIP_CONDENSED_REDUCED") && s->nx0 == s->nxb &&
@@ -909,23 +796,23 @@ int allocate(gar_hip_solver *s) {
   }
   if (s->seg_bwd_kernel) {
     const gar::HostLayout &f = *s->flay;
-    HIP_TRY(dev_zalloc(&s->d_fac2, sizeof(double) * (size_t)f.fac_doubles * B));
-    HIP_TRY(gar_dev_malloc((void **)&s->d_meta2, sizeof(gar_stage_meta) * f.meta.size()));
-    HIP_TRY(hipMemcpy(s->d_meta2, f.meta.data(), sizeof(gar_stage_meta) * f.meta.size(), hipMemcpyHostToDevice));
+    HIP_TRY(s->buf.d_fac2.zalloc((size_t)f.fac_doubles * B));
+    HIP_TRY(s->buf.d_meta2.alloc(f.meta.size()));
+    HIP_TRY(hipMemcpy(s->buf.d_meta2, f.meta.data(), sizeof(gar_stage_meta) * f.meta.size(), hipMemcpyHostToDevice));
     HIP_TRY(max_lds(s->seg_bwd_kernel, s->seg_lds_doubles));
     HIP_TRY(max_lds(gar::gar_leg_param_chain, gar::leg_chain_lds_doubles(s->dims5[0])));
     HIP_TRY(max_lds(gar::gar_leg_param_stage, gar::leg_stage_lds_doubles(s->dims5[0], s->dims5[1])));
   }
   if (s->fold) {
     const gar::HostLayout &f = *s->flay;
-    HIP_TRY(dev_zalloc(&s->d_prob2, sizeof(double) * (size_t)f.prob_doubles * B));
-    HIP_TRY(dev_zalloc(&s->d_fac2, sizeof(double) * (size_t)f.fac_doubles * B));
-    HIP_TRY(gar_dev_malloc((void **)&s->d_meta2, sizeof(gar_stage_meta) * f.meta.size()));
-    HIP_TRY(hipMemcpy(s->d_meta2, f.meta.data(), sizeof(gar_stage_meta) * f.meta.size(), hipMemcpyHostToDevice));
+    HIP_TRY(s->buf.d_prob2.zalloc((size_t)f.prob_doubles * B));
+    HIP_TRY(s->buf.d_fac2.zalloc((size_t)f.fac_doubles * B));
+    HIP_TRY(s->buf.d_meta2.alloc(f.meta.size()));
+    HIP_TRY(hipMemcpy(s->buf.d_meta2, f.meta.data(), sizeof(gar_stage_meta) * f.meta.size(), hipMemcpyHostToDevice));
     if (s->cseg_on) {
       const size_t units = B * (size_t)s->legs_per_rank;
-      HIP_TRY(gar_dev_malloc((void **)&s->d_cseg_resume, sizeof(int) * units));
-      HIP_TRY(hipMemset(s->d_cseg_resume, 0xff, sizeof(int) * units));
+      HIP_TRY(s->buf.d_cseg_resume.alloc(units));
+      HIP_TRY(hipMemset(s->buf.d_cseg_resume, 0xff, sizeof(int) * units));
       for (auto k : s->cseg.backward)
         HIP_TRY(max_lds(k, s->cseg.backward_lds_doubles));
       HIP_TRY(max_lds(s->cseg.leg_end, s->cseg.leg_end_lds_doubles));
@@ -933,17 +820,17 @@ int allocate(gar_hip_solver *s) {
       HIP_TRY(max_lds(s->cseg.stage, s->cseg.stage_lds_doubles));
     }
   }
-  s->fold_expanded = s->coupled_known = false;
+  s->buf.fold_expanded = s->buf.coupled_known = false;
   const size_t staging = sizeof(double) * (size_t)s->prob_doubles * B;
   if (staging <= ((size_t)1 << 30)) {
-    HIP_TRY(gar_host_malloc((void **)&s->h_prob, staging, hipHostMallocDefault));
-    std::memset(s->h_prob, 0, staging);
-    s->staged = true;
+    HIP_TRY(s->buf.h_prob.alloc((size_t)s->prob_doubles * B, hipHostMallocDefault));
+    std::memset(s->buf.h_prob, 0, staging);
+    s->buf.staged = true;
     const char *nt = gar_option("GAR_HIP_STAGE_NT");
-    s->stage_nt = nt && nt[0] ? nt[0] == '1' : sizeof(double) * (size_t)s->prob_doubles >= ((size_t)12 << 20);
+    s->buf.stage_nt = nt && nt[0] ? nt[0] == '1' : sizeof(double) * (size_t)s->prob_doubles >= ((size_t)12 << 20);
   }
-  s->dirty_iv.assign(B, {});
-  s->dirty = false;
+  s->buf.dirty_iv.assign(B, {});
+  s->buf.dirty = false;
   if (s->dense) {
     HIP_TRY(max_lds(gar::gar_backward_dense, s->dense_lds.total));
     return GAR_HIP_OK;
@@ -1080,37 +967,33 @@ double gar_hip_stream_ceiling_ms(int device, int batch, int horizon, int64_t in_
   int prev = 0;
   if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device) != hipSuccess)
     return -1.0;
-  gar::gar_double2 *in = nullptr, *out = nullptr;
-  double *sink = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
   double best = -1.0;
-  const size_t nin = (size_t)batch * horizon * in_pieces * 16, nout = (size_t)batch * horizon * out_pieces * 16;
-  if (gar_dev_malloc((void **)&in, nin) == hipSuccess && gar_dev_malloc((void **)&out, nout) == hipSuccess &&
-      gar_dev_malloc((void **)&sink, (size_t)batch * 64 * 8) == hipSuccess && hipMemset(in, 0, nin) == hipSuccess &&
-      hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-    for (int r = 0; r < reps + 1; ++r) { // first launch: warm-up
-      (void)hipEventRecord(e0, nullptr);
-      if (reps_ahead2)
-        hipLaunchKernelGGL((gar::gar_stream_sweep2<32, 28>), dim3((unsigned)batch), dim3(64), 0, nullptr, in, out, sink,
-                           horizon, in_pieces, out_pieces);
-      else
-        hipLaunchKernelGGL((gar::gar_stream_sweep<32, 28>), dim3((unsigned)batch), dim3(64), 0, nullptr, in, out, sink,
-                           horizon, in_pieces, out_pieces, stage_major);
-      (void)hipEventRecord(e1, nullptr);
-      float ms = 0.f;
-      if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {
-        best = -1.0;
-        break;
+  const size_t nin = (size_t)batch * horizon * in_pieces, nout = (size_t)batch * horizon * out_pieces; // 16-byte pieces
+  { // (the owners let go at the end of this block, with `device` still current)
+    DevBuf<gar::gar_double2> in, out;
+    DevBuf<double> sink;
+    Event e0, e1;
+    if (in.alloc(nin) == hipSuccess && out.alloc(nout) == hipSuccess && sink.alloc((size_t)batch * 64) == hipSuccess &&
+        hipMemset(in, 0, nin * 16) == hipSuccess && e0.create() == hipSuccess && e1.create() == hipSuccess) {
+      for (int r = 0; r < reps + 1; ++r) { // first launch: warm-up
+        (void)hipEventRecord(e0, nullptr);
+        if (reps_ahead2)
+          hipLaunchKernelGGL((gar::gar_stream_sweep2<32, 28>), dim3((unsigned)batch), dim3(64), 0, nullptr, in.get(), out.get(),
+                             sink.get(), horizon, in_pieces, out_pieces);
+        else
+          hipLaunchKernelGGL((gar::gar_stream_sweep<32, 28>), dim3((unsigned)batch), dim3(64), 0, nullptr, in.get(), out.get(),
+                             sink.get(), horizon, in_pieces, out_pieces, stage_major);
+        (void)hipEventRecord(e1, nullptr);
+        float ms = 0.f;
+        if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {
+          best = -1.0;
+          break;
+        }
+        if (r > 0 && (best < 0.0 || ms < best))
+          best = ms;
       }
-      if (r > 0 && (best < 0.0 || ms < best))
-        best = ms;
     }
   }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(in);
-  (void)hipFree(out);
-  (void)hipFree(sink);
   (void)hipSetDevice(prev);
   return best;
 }
@@ -1123,31 +1006,28 @@ double gar_hip_copy_ceiling_ms(int device, int64_t bytes_moved, int reps) {
   int prev = 0;
   if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device) != hipSuccess)
     return -1.0;
-  gar::gar_double2 *src = nullptr, *dst = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
   double best = -1.0;
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-  if (gar_dev_malloc((void **)&src, (size_t)n * 16) == hipSuccess && gar_dev_malloc((void **)&dst, (size_t)n * 16) == hipSuccess &&
-      hipMemset(src, 0, (size_t)n * 16) == hipSuccess && hipEventCreate(&e0) == hipSuccess &&
-      hipEventCreate(&e1) == hipSuccess) {
-    for (int r = 0; r < reps + 1; ++r) { // first launch: warm-up
-      (void)hipEventRecord(e0, nullptr);
-      hipLaunchKernelGGL(gar::gar_plain_copy, dim3((unsigned)(cus * 64)), dim3(256), 0, nullptr, src, dst, n);
-      (void)hipEventRecord(e1, nullptr);
-      float ms = 0.f;
-      if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {
-        best = -1.0;
-        break;
+  {
+    DevBuf<gar::gar_double2> src, dst;
+    Event e0, e1;
+    if (src.alloc((size_t)n) == hipSuccess && dst.alloc((size_t)n) == hipSuccess &&
+        hipMemset(src, 0, (size_t)n * 16) == hipSuccess && e0.create() == hipSuccess && e1.create() == hipSuccess) {
+      for (int r = 0; r < reps + 1; ++r) { // first launch: warm-up
+        (void)hipEventRecord(e0, nullptr);
+        hipLaunchKernelGGL(gar::gar_plain_copy, dim3((unsigned)(cus * 64)), dim3(256), 0, nullptr, src.get(), dst.get(), n);
+        (void)hipEventRecord(e1, nullptr);
+        float ms = 0.f;
+        if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {
+          best = -1.0;
+          break;
+        }
+        if (r > 0 && (best < 0.0 || ms < best))
+          best = ms;
       }
-      if (r > 0 && (best < 0.0 || ms < best))
-        best = ms;
     }
   }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(src);
-  (void)hipFree(dst);
   (void)hipSetDevice(prev);
   return best;
 }
@@ -1192,10 +1072,7 @@ gar_hip_solver *create_impl(int device, int horizon, const int32_t *dims5, int n
   normalise_terminal(s);
   DeviceGuard guard_(device); // the caller's current device is restored on return
   auto give_up = [s]() -> gar_hip_solver * { // the one way out on failure (g_last_error says why)
-    free_device(s);
-    if (s->own_stream)
-      (void)hipStreamDestroy(s->own_stream);
-    delete s;
+    delete s; // (inside guard_: what it owns is released with its device current)
     return nullptr;
   };
   {
@@ -1207,7 +1084,7 @@ gar_hip_solver *create_impl(int device, int horizon, const int32_t *dims5, int n
   }
   if (configure(s) != GAR_HIP_OK)
     return give_up();
-  if (hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking) != hipSuccess) {
+  if (s->own_stream.create(hipStreamNonBlocking) != hipSuccess) {
     fail(GAR_HIP_ERR_DEVICE, "hipStreamCreate failed");
     return give_up();
   }
@@ -1260,36 +1137,13 @@ void gar_hip_solver_destroy(gar_hip_solver *s) {
     multi_destroy(s);
     return;
   }
-  GAR_GUARD(s);
-  (void)hipStreamSynchronize(s->stream);
-  for (int h = 0; h < 2; ++h)
-    if (s->pipe_stream[h]) {
-      (void)hipStreamSynchronize(s->pipe_stream[h]);
-      (void)hipStreamDestroy(s->pipe_stream[h]);
-      (void)hipEventDestroy(s->pipe_evB[h]);
-      (void)hipEventDestroy(s->pipe_evF[h]);
-      for (auto &e : s->pipe_evT[h])
-        (void)hipEventDestroy(e);
-    }
-  if (s->pipe_evFork)
-    (void)hipEventDestroy(s->pipe_evFork);
-  free_device(s);
-  if (s->own_stream)
-    (void)hipStreamDestroy(s->own_stream);
-  for (auto &e : s->ev)
-    if (e)
-      (void)hipEventDestroy(e);
-  if (s->aux_stream) {
-    (void)hipStreamSynchronize(s->aux_stream);
-    (void)hipStreamDestroy(s->aux_stream);
-    (void)hipEventDestroy(s->ev_main);
-    (void)hipEventDestroy(s->ev_pref);
-  }
-  if (s->h_status) {
-    (void)hipHostFree(s->h_status);
-    (void)hipEventDestroy(s->ev_status);
-    (void)hipEventDestroy(s->ev_sol);
-  }
+  GAR_GUARD(s); // (encloses the delete: buffers, streams and events are released with the solver's device current)
+  (void)hipStreamSynchronize(s->stream); // every stream that may hold work idle first, then the owners let go
+  for (const Stream &h : s->pipe.stream)
+    if (h)
+      (void)hipStreamSynchronize(h);
+  if (s->lazy.aux_stream)
+    (void)hipStreamSynchronize(s->lazy.aux_stream);
   delete s;
 }
 
@@ -1384,19 +1238,19 @@ static int upload_stage_dev(gar_hip_solver *s, int b, int t, const double *Q, co
   auto put = [&](int64_t off, const double *src, int64_t n) {
     if (n <= 0)
       return;
-    if (!s->staged) {
+    if (!s->buf.staged) {
       rc |= write_block(s, b, off, src, n);
       return;
     }
-    double *dst = s->h_prob + (int64_t)b * s->prob_doubles + off;
+    double *dst = s->buf.h_prob + (int64_t)b * s->prob_doubles + off;
     if (src)
-      stage_copy(dst, src, (size_t)n, s->stage_nt);
+      stage_copy(dst, src, (size_t)n, s->buf.stage_nt);
     else
       std::memset(dst, 0, sizeof(double) * (size_t)n);
   };
   if (s->qr_packed && t < s->horizon) { // Q, R: their lower triangles, packed, in the first n (n + 1) / 2 doubles of the block
-    if (s->staged) {
-      double *rec = s->h_prob + (int64_t)b * s->prob_doubles + base;
+    if (s->buf.staged) {
+      double *rec = s->buf.h_prob + (int64_t)b * s->prob_doubles + base;
       pack_lower(rec + o.Q, Q, nx, nx, 0.0);
       pack_lower(rec + o.R, R, nu, nu, 0.0);
     } else {
@@ -1428,7 +1282,7 @@ static int upload_stage_dev(gar_hip_solver *s, int b, int t, const double *Q, co
     put(base + o.Gv, Gv, (int64_t)nc * nth_st);
     put(base + o.gamma, gamma, nth_st);
   }
-  if (s->staged) {
+  if (s->buf.staged) {
     mark_dirty(s, b, base, base + gar_knot_doubles(nx, nu, nc, nx2, nth_st));
     return flush_if_grown(s, b);
   }
@@ -1468,15 +1322,15 @@ int gar_hip_upload_packed(gar_hip_solver *s, int b0, int nb, const double *packe
     return GAR_HIP_OK;
   }
   const size_t bytes = sizeof(double) * (size_t)s->prob_doubles * nb;
-  if (s->staged) {
-    std::memcpy(s->h_prob + (int64_t)b0 * s->prob_doubles, packed, bytes);
+  if (s->buf.staged) {
+    std::memcpy(s->buf.h_prob + (int64_t)b0 * s->prob_doubles, packed, bytes);
     for (int b = b0; b < b0 + nb; ++b) {
-      s->dirty_iv[(size_t)b].clear();
+      s->buf.dirty_iv[(size_t)b].clear();
       mark_dirty(s, b, 0, s->prob_doubles);
     }
     return GAR_HIP_OK;
   }
-  HIP_TRY(hipMemcpyAsync(s->d_prob + (int64_t)b0 * s->prob_doubles, packed, bytes,
+  HIP_TRY(hipMemcpyAsync(s->buf.d_prob + (int64_t)b0 * s->prob_doubles, packed, bytes,
                          hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return GAR_HIP_OK;
@@ -1489,7 +1343,7 @@ int gar_hip_upload_packed_device(gar_hip_solver *s, int b0, int nb, const double
     return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_packed_device: bad argument");
   if (int rc = commit(s)) // staged host data first, then the device copy wins
     return rc;
-  HIP_TRY(hipMemcpyAsync(s->d_prob + (int64_t)b0 * s->prob_doubles, packed_dev,
+  HIP_TRY(hipMemcpyAsync(s->buf.d_prob + (int64_t)b0 * s->prob_doubles, packed_dev,
                          sizeof(double) * (size_t)s->prob_doubles * nb, hipMemcpyDeviceToDevice,
                          s->stream));
   // (the staging area stays in use: commit() flushes only the ranges the host writes later)
@@ -1516,7 +1370,7 @@ int gar_hip_commit(gar_hip_solver *s) {
 
 double *gar_hip_device_problems(gar_hip_solver *s) {
   pipe_autojoin(s);
-  return s ? s->d_prob : nullptr;
+  return s ? s->buf.d_prob : nullptr;
 }
 double *gar_hip_device_factors(gar_hip_solver *s) {
   if (s && s->multi) // (the records live on several devices)
@@ -1524,14 +1378,14 @@ double *gar_hip_device_factors(gar_hip_solver *s) {
   if (s && s->fold) { // the caller-visible records of a folded solver are formed on request
     GAR_GUARD(s);
     (void)ensure_expanded(s);
-  } else if (s && s->pipe_forked) { // (a pipelined sweep: the caller's stream is ordered behind it before the pointer leaves)
+  } else if (s && s->pipe.forked) { // (a pipelined sweep: the caller's stream is ordered behind it before the pointer leaves)
     GAR_GUARD(s);
   }
-  return s ? s->d_fac : nullptr;
+  return s ? s->buf.d_fac : nullptr;
 }
 double *gar_hip_device_solutions(gar_hip_solver *s) {
   pipe_autojoin(s); // (a pipelined sweep: the caller's stream is ordered behind it before the pointer leaves)
-  return s ? s->d_sol : nullptr;
+  return s ? s->buf.d_sol : nullptr;
 }
 
 int gar_hip_backward_legs_async(gar_hip_solver *s, double mueq) {
@@ -1553,8 +1407,8 @@ int gar_hip_backward_legs_async(gar_hip_solver *s, double mueq) {
                                         " on constrained knots)");
   GAR_MULTI(s, multi_backward_legs(s, mueq));
   s->eager_fwd = false;
-  if (s->ev_pref) { // a read-back of the previous sweep's gains may still be in flight on the second stream
-    HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_pref, 0));
+  if (s->lazy.ev_pref) { // a read-back of the previous sweep's gains may still be in flight on the second stream
+    HIP_TRY(hipStreamWaitEvent(s->stream, s->lazy.ev_pref, 0));
     s->pref_b = -1;
   }
   if (int rc = commit(s))
@@ -1658,7 +1512,8 @@ int gar_hip_set_pipeline(gar_hip_solver *s, int halves) {
                                              s->kernel_name + ")");
   if (int rc = pipe_plan(s, s->lean_fwd_used))
     return rc;
-  if (!s->pipe_stream[0]) {
+  if (!s->pipe.stream[0]) { // first request served: the group is made whole or not at all
+    gar::PipeState fresh;
     HIP_TRY(hipFuncSetAttribute((const void *)s->lean_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)s->lean_fwd_lds_bytes));
     HIP_TRY(hipFuncSetAttribute((const void *)s->wave_half_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1674,16 +1529,17 @@ int gar_hip_set_pipeline(gar_hip_solver *s, int halves) {
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         const bool plain = pp ? pp[0] == '0' : (mq && std::atoi(mq) >= 8);
         if (plain)
-          HIP_TRY(hipStreamCreateWithFlags(&s->pipe_stream[h], hipStreamNonBlocking));
+          HIP_TRY(fresh.stream[h].create(hipStreamNonBlocking));
         else
-          HIP_TRY(hipStreamCreateWithPriority(&s->pipe_stream[h], hipStreamNonBlocking, h == 0 ? 0 : hi));
+          HIP_TRY(fresh.stream[h].create_with_priority(hipStreamNonBlocking, h == 0 ? 0 : hi));
       }
-      HIP_TRY(hipEventCreateWithFlags(&s->pipe_evB[h], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&s->pipe_evF[h], hipEventDisableTiming));
-      for (auto &e : s->pipe_evT[h])
-        HIP_TRY(hipEventCreate(&e));
+      HIP_TRY(fresh.evB[h].create(hipEventDisableTiming));
+      HIP_TRY(fresh.evF[h].create(hipEventDisableTiming));
+      for (Event &e : fresh.evT[h])
+        HIP_TRY(e.create());
     }
-    HIP_TRY(hipEventCreateWithFlags(&s->pipe_evFork, hipEventDisableTiming));
+    HIP_TRY(fresh.evFork.create(hipEventDisableTiming));
+    s->pipe = std::move(fresh);
   }
   s->pipe_halves = 2;
   s->pipe_requested = automatic ? -1 : 2;
@@ -1755,13 +1611,18 @@ int gar_hip_backward_blocks(gar_hip_solver *s, const double *const *blocks, cons
     if (int rc = launch_condensed(s))
       return rc;
   }
-  if (!s->h_status) {
-    HIP_TRY(gar_host_malloc((void **)&s->h_status, sizeof(int) * (size_t)s->batch, hipHostMallocDefault));
-    HIP_TRY(hipEventCreateWithFlags(&s->ev_status, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&s->ev_sol, hipEventDisableTiming));
+  if (!s->lazy.h_status) {
+    PinnedBuf<int> h;
+    Event status, sol;
+    HIP_TRY(h.alloc((size_t)s->batch, hipHostMallocDefault));
+    HIP_TRY(status.create(hipEventDisableTiming));
+    HIP_TRY(sol.create(hipEventDisableTiming));
+    s->lazy.h_status = std::move(h);
+    s->lazy.ev_status = std::move(status);
+    s->lazy.ev_sol = std::move(sol);
   }
-  HIP_TRY(hipMemcpyAsync(s->h_status, s->d_status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipEventRecord(s->ev_status, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->lazy.h_status, s->buf.d_status, sizeof(int) * (size_t)s->batch, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipEventRecord(s->lazy.ev_status, s->stream));
   if (s->num_legs == 1)
     if (int rc = prefetch_impl(s, 0))
       return rc;
@@ -1772,23 +1633,23 @@ int gar_hip_backward_blocks(gar_hip_solver *s, const double *const *blocks, cons
     const size_t nsol = (size_t)u.sol_doubles, ngain = (size_t)(u.ff_all_doubles + u.fb_all_doubles);
     // by a kernel's own stores into the pinned buffer: the copy engine is busy with the gains (3.7 / 9.4 MB) and a
     // hipMemcpyAsync would queue behind them (measured: profiles/r04_seam_eager_rollout_ab.json)
-    double *dst = s->h_results + (s->padded ? nsol + ngain : 0);
+    double *dst = s->buf.h_results + (s->padded ? nsol + ngain : 0);
     const unsigned nblk = (unsigned)std::min<int64_t>((s->sol_doubles + 255) / 256, 256);
-    hipLaunchKernelGGL(gar::gar_store_to_host, dim3(nblk), dim3(256), 0, s->stream, dst, s->d_sol, (long long)s->sol_doubles);
+    hipLaunchKernelGGL(gar::gar_store_to_host, dim3(nblk), dim3(256), 0, s->stream, dst, s->buf.d_sol.get(), (long long)s->sol_doubles);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(s->ev_sol, s->stream));
-  HIP_TRY(hipEventSynchronize(s->ev_status));
+  HIP_TRY(hipEventRecord(s->lazy.ev_sol, s->stream));
+  HIP_TRY(hipEventSynchronize(s->lazy.ev_status));
   int nf = 0;
   for (int b = 0; b < s->batch; ++b)
-    nf += (s->h_status[b] != 0);
+    nf += (s->lazy.h_status[b] != 0);
   s->last_failed = nf;
   if (nf > 0) {
     // the roll-out, the solution's copy and the gains' read-back of the FAILED sweep are already enqueued: let them
     // finish and disarm the "already in flight" shortcuts, so that a later fetch does its own work (and nobody is
     // handed these gains as if the sweep had succeeded)
-    if (s->ev_pref)
-      HIP_TRY(hipEventSynchronize(s->ev_pref));
+    if (s->lazy.ev_pref)
+      HIP_TRY(hipEventSynchronize(s->lazy.ev_pref));
     s->pref_b = -1;
     s->eager_fwd = false;
     return fail(GAR_HIP_ERR_FACTOR, "Failed stage LDL factorization (" + std::to_string(nf) + " problem(s))");
@@ -1803,7 +1664,7 @@ int gar_hip_num_failed(gar_hip_solver *s) {
     return 0;
   GAR_MULTI(s, multi_num_failed(s));
   std::vector<int> st((size_t)s->batch);
-  if (hipMemcpyAsync(st.data(), s->d_status, sizeof(int) * st.size(), hipMemcpyDeviceToHost,
+  if (hipMemcpyAsync(st.data(), s->buf.d_status, sizeof(int) * st.size(), hipMemcpyDeviceToHost,
                      s->stream) != hipSuccess ||
       hipStreamSynchronize(s->stream) != hipSuccess)
     return -1;
@@ -1875,14 +1736,14 @@ int gar_hip_forward(gar_hip_solver *s, const double *theta) {
     return multi_sync(s);
   }
   if (s->eager_fwd) { // enqueued behind the sweep by gar_hip_backward_blocks (no parameter: theta has no say)
-    HIP_TRY(hipEventSynchronize(s->ev_sol));
+    HIP_TRY(hipEventSynchronize(s->lazy.ev_sol));
     return GAR_HIP_OK;
   }
   const double *th = nullptr;
   if (theta && s->nth0 > 0 && s->num_legs == 1) {
-    HIP_TRY(hipMemcpyAsync(s->d_theta, theta, sizeof(double) * (size_t)s->nth0 * s->batch,
+    HIP_TRY(hipMemcpyAsync(s->buf.d_theta, theta, sizeof(double) * (size_t)s->nth0 * s->batch,
                            hipMemcpyHostToDevice, s->stream));
-    th = s->d_theta;
+    th = s->buf.d_theta;
   }
   if (int rc = launch_forward(s, th))
     return rc;
@@ -1891,8 +1752,8 @@ int gar_hip_forward(gar_hip_solver *s, const double *theta) {
 }
 
 int64_t gar_hip_boundary_doubles(const gar_hip_solver *s) { return s ? s->tuple_doubles : 0; }
-double *gar_hip_device_boundary_local(gar_hip_solver *s) { return s ? s->d_bound_local : nullptr; }
-double *gar_hip_device_boundary_all(gar_hip_solver *s) { return s ? s->d_bound_all : nullptr; }
+double *gar_hip_device_boundary_local(gar_hip_solver *s) { return s ? s->buf.d_bound_local : nullptr; }
+double *gar_hip_device_boundary_all(gar_hip_solver *s) { return s ? s->buf.bound_all() : nullptr; }
 
 int gar_hip_set_refinement(gar_hip_solver *s, double thr, int max_steps) {
   if (!s || max_steps < 0)
@@ -1910,7 +1771,7 @@ int gar_hip_condensed_info(gar_hip_solver *s, int b, double out[2]) {
   GAR_MULTI(s, gar_hip_condensed_info(s->multi->subs[0], b, out)); // (solved redundantly on every device)
   if (s->num_legs < 2 || !out)
     return fail(GAR_HIP_ERR_ARG, "condensed info needs leg mode");
-  const double *info = s->d_cscratch + (int64_t)b * s->cscratch_doubles + cond_info_off(s);
+  const double *info = s->buf.d_cscratch + (int64_t)b * s->cscratch_doubles + cond_info_off(s);
   if (int rc = d2h(s, out, info, 2))
     return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1919,7 +1780,7 @@ int gar_hip_condensed_info(gar_hip_solver *s, int b, double out[2]) {
 
 static int get_solution_dev(gar_hip_solver *s, int b, double *xs, double *us, double *vs,
                          double *lbdas) {
-  const double *base = s->d_sol + (int64_t)b * s->sol_doubles;
+  const double *base = s->buf.d_sol + (int64_t)b * s->sol_doubles;
   int rc = d2h(s, xs, base + s->sol_x, s->sol_u - s->sol_x);
   rc |= d2h(s, us, base + s->sol_u, s->sol_v - s->sol_u);
   rc |= d2h(s, vs, base + s->sol_v, s->sol_l - s->sol_v);
@@ -1939,7 +1800,7 @@ static int get_gains_dev(gar_hip_solver *s, int b, int t, double *ff, double *fb
   const gar_stage_meta &m = s->meta[t];
   const int nx2r = s->dense ? 2 * m.nx2 : m.nx2; // stage-dense solver: rows [K; Z; L; Y]
   const gar_factor_offsets o = gar_factor_layout(m.nx, m.nu, m.nc, nx2r, m.nth);
-  const double *rec = s->d_fac + (int64_t)b * s->fac_doubles + m.fac_off;
+  const double *rec = s->buf.d_fac + (int64_t)b * s->fac_doubles + m.fac_off;
   const int64_t nr = (int64_t)m.nu + m.nc + nx2r;
   int rc = d2h(s, ff, rec + o.ff, nr);
   std::vector<double> tmp;
@@ -2006,34 +1867,30 @@ static int fetch_results_impl(gar_hip_solver *s, int b, int what, int t_lo, int 
   const gar::HostLayout &u = caller_layout(s);
   const size_t nsol = (size_t)u.sol_doubles, ngain = (size_t)(u.ff_all_doubles + u.fb_all_doubles);
   const size_t nscratch = s->padded ? (size_t)s->sol_doubles : 0;
-  if (!s->h_results) { // first use: the buffers live as long as the solver's layout
+  if (!s->buf.h_results) { // first use: the buffers live as long as the solver's layout
     // all three or none: a partial failure must not leave h_results set with the device buffers missing
-    double *h = nullptr, *dg = nullptr;
-    long long *dgo = nullptr;
-    hipError_t e = gar_host_malloc((void **)&h, sizeof(double) * (nsol + ngain + nscratch), hipHostMallocDefault);
+    PinnedBuf<double> h;
+    DevBuf<double> dg;
+    DevBuf<long long> dgo;
+    hipError_t e = h.alloc(nsol + ngain + nscratch, hipHostMallocDefault);
     if (e == hipSuccess)
-      e = gar_dev_malloc((void **)&dg, sizeof(double) * std::max<size_t>(ngain, 1));
+      e = dg.alloc(std::max<size_t>(ngain, 1));
     if (e == hipSuccess)
-      e = gar_dev_malloc((void **)&dgo, sizeof(long long) * u.gain_off.size());
+      e = dgo.alloc(u.gain_off.size());
     if (e == hipSuccess)
       e = hipMemcpyAsync(dgo, u.gain_off.data(), sizeof(long long) * u.gain_off.size(), hipMemcpyHostToDevice,
                          s->stream);
-    if (e != hipSuccess) {
-      if (h)
-        (void)hipHostFree(h);
-      (void)hipFree(dg);
-      (void)hipFree(dgo);
+    if (e != hipSuccess)
       return fail(GAR_HIP_ERR_DEVICE, std::string("gar_hip_fetch_results: ") + hipGetErrorString(e));
-    }
     std::memset(h, 0, sizeof(double) * (nsol + ngain + nscratch)); // (alignment padding inside the records reads as zero)
-    s->h_results = h;
-    s->d_gains = dg;
-    s->d_gain_off = dgo;
+    s->buf.h_results = std::move(h);
+    s->buf.d_gains = std::move(dg);
+    s->buf.d_gain_off = std::move(dgo);
   }
   if ((what & 2) && s->pref_b == b && !gains_base && t_lo == 0 && t_hi == s->horizon + 1) {
     // the gains are already on their way (gar_hip_prefetch_gains): wait for them; what collapseFeedback changed
     // since -- stage 0 -- comes again
-    HIP_TRY(hipEventSynchronize(s->ev_pref));
+    HIP_TRY(hipEventSynchronize(s->lazy.ev_pref));
     s->pref_b = -1;
     if (!s->pref_collapsed)
       what &= ~2;
@@ -2041,47 +1898,47 @@ static int fetch_results_impl(gar_hip_solver *s, int b, int what, int t_lo, int 
       t_hi = 1;
   }
   if ((what & 2) && t_hi > t_lo) { // device-side gather (fbT2 -> row-major, dummy rows / columns dropped), then ONE device-to-host copy
-    if (s->pref_b >= 0 && s->ev_pref) {
+    if (s->pref_b >= 0 && s->lazy.ev_pref) {
       // a read-back started by gar_hip_prefetch_gains (of another problem, or of this one over another range) may
       // still be writing d_gains / h_results on the second stream: this gather and copy reuse both
-      HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_pref, 0));
-      HIP_TRY(hipEventSynchronize(s->ev_pref)); // (h_results is host memory: the caller may read it right after)
+      HIP_TRY(hipStreamWaitEvent(s->stream, s->lazy.ev_pref, 0));
+      HIP_TRY(hipEventSynchronize(s->lazy.ev_pref)); // (h_results is host memory: the caller may read it right after)
       s->pref_b = -1;
     }
     if (int rc = ensure_expanded(s))
       return rc;
     const bool t2 = records_t2(s, b);
     hipLaunchKernelGGL(gar::gar_gather_gains, dim3((unsigned)(t_hi - t_lo)), dim3(256), 0, s->stream,
-                       s->d_meta, s->d_fac + (int64_t)b * s->fac_doubles, s->d_gains,
-                       s->d_gains + u.ff_all_doubles, s->d_gain_off, s->horizon, t2 ? 1 : 0,
+                       s->buf.d_meta.get(), s->buf.d_fac + (int64_t)b * s->fac_doubles, s->buf.d_gains.get(),
+                       s->buf.d_gains + u.ff_all_doubles, s->buf.d_gain_off.get(), s->horizon, t2 ? 1 : 0,
                        s->dense ? 1 : 0, s->padded ? s->unx : 0, s->padded ? s->unu : 0, t_lo);
     HIP_TRY(hipGetLastError());
-    double *hg = (gains_base ? gains_base : s->h_results) + nsol;
+    double *hg = (gains_base ? gains_base : s->buf.h_results) + nsol;
     if (t_lo == 0 && t_hi == s->horizon + 1) {
-      HIP_TRY(hipMemcpyAsync(hg, s->d_gains, sizeof(double) * ngain, hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(hipMemcpyAsync(hg, s->buf.d_gains, sizeof(double) * ngain, hipMemcpyDeviceToHost, s->stream));
     } else { // the two slices of this stage range
       const std::vector<long long> &go = u.gain_off;
       const long long f0 = go[2 * (size_t)t_lo], f1 = t_hi <= s->horizon ? go[2 * (size_t)t_hi] : u.ff_all_doubles;
       const long long b0 = go[2 * (size_t)t_lo + 1], b1 = t_hi <= s->horizon ? go[2 * (size_t)t_hi + 1] : u.fb_all_doubles;
       if (f1 > f0)
-        HIP_TRY(hipMemcpyAsync(hg + f0, s->d_gains + f0, sizeof(double) * (size_t)(f1 - f0), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(hg + f0, s->buf.d_gains + f0, sizeof(double) * (size_t)(f1 - f0), hipMemcpyDeviceToHost, s->stream));
       if (b1 > b0)
-        HIP_TRY(hipMemcpyAsync(hg + u.ff_all_doubles + b0, s->d_gains + u.ff_all_doubles + b0,
+        HIP_TRY(hipMemcpyAsync(hg + u.ff_all_doubles + b0, s->buf.d_gains + u.ff_all_doubles + b0,
                                sizeof(double) * (size_t)(b1 - b0), hipMemcpyDeviceToHost, s->stream));
     }
   }
   const bool sol_there = (what & 1) && s->eager_fwd && b == 0; // copied behind the eager roll-out (gar_hip_backward_blocks)
   if ((what & 1) && !sol_there)
-    HIP_TRY(hipMemcpyAsync(s->h_results + (s->padded ? nsol + ngain : 0), s->d_sol + (int64_t)b * s->sol_doubles,
+    HIP_TRY(hipMemcpyAsync(s->buf.h_results + (s->padded ? nsol + ngain : 0), s->buf.d_sol + (int64_t)b * s->sol_doubles,
                            sizeof(double) * (size_t)s->sol_doubles, hipMemcpyDeviceToHost, s->stream));
   if (!sync)
     return GAR_HIP_OK;
   if (sol_there && what == 1)
-    HIP_TRY(hipEventSynchronize(s->ev_sol));
+    HIP_TRY(hipEventSynchronize(s->lazy.ev_sol));
   else
     HIP_TRY(hipStreamSynchronize(s->stream));
   if ((what & 1) && s->padded)
-    strip_solution_rec(s, s->h_results + nsol + ngain, s->h_results);
+    strip_solution_rec(s, s->buf.h_results + nsol + ngain, s->buf.h_results);
   return GAR_HIP_OK;
 }
 
@@ -2090,22 +1947,27 @@ static int fetch_results_impl(gar_hip_solver *s, int b, int what, int t_lo, int 
 static int prefetch_impl(gar_hip_solver *s, int b) {
   if (int rc = fetch_results_impl(s, b, 0, 0, 0, nullptr, false)) // the buffers, on first use
     return rc;
-  if (!s->aux_stream) {
-    HIP_TRY(hipStreamCreateWithFlags(&s->aux_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&s->ev_main, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&s->ev_pref, hipEventDisableTiming));
+  if (!s->lazy.aux_stream) {
+    Stream aux;
+    Event main, pref;
+    HIP_TRY(aux.create(hipStreamNonBlocking));
+    HIP_TRY(main.create(hipEventDisableTiming));
+    HIP_TRY(pref.create(hipEventDisableTiming));
+    s->lazy.aux_stream = std::move(aux);
+    s->lazy.ev_main = std::move(main);
+    s->lazy.ev_pref = std::move(pref);
   }
   const gar::HostLayout &u = caller_layout(s);
   const size_t nsol = (size_t)u.sol_doubles, ngain = (size_t)(u.ff_all_doubles + u.fb_all_doubles);
-  HIP_TRY(hipEventRecord(s->ev_main, s->stream));
-  HIP_TRY(hipStreamWaitEvent(s->aux_stream, s->ev_main, 0));
-  hipLaunchKernelGGL(gar::gar_gather_gains, dim3((unsigned)(s->horizon + 1)), dim3(256), 0, s->aux_stream, s->d_meta,
-                     s->d_fac + (int64_t)b * s->fac_doubles, s->d_gains, s->d_gains + u.ff_all_doubles, s->d_gain_off,
+  HIP_TRY(hipEventRecord(s->lazy.ev_main, s->stream));
+  HIP_TRY(hipStreamWaitEvent(s->lazy.aux_stream, s->lazy.ev_main, 0));
+  hipLaunchKernelGGL(gar::gar_gather_gains, dim3((unsigned)(s->horizon + 1)), dim3(256), 0, s->lazy.aux_stream, s->buf.d_meta.get(),
+                     s->buf.d_fac + (int64_t)b * s->fac_doubles, s->buf.d_gains.get(), s->buf.d_gains + u.ff_all_doubles, s->buf.d_gain_off.get(),
                      s->horizon, records_t2(s, b) ? 1 : 0, s->dense ? 1 : 0, s->padded ? s->unx : 0,
                      s->padded ? s->unu : 0, 0);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(s->h_results + nsol, s->d_gains, sizeof(double) * ngain, hipMemcpyDeviceToHost, s->aux_stream));
-  HIP_TRY(hipEventRecord(s->ev_pref, s->aux_stream));
+  HIP_TRY(hipMemcpyAsync(s->buf.h_results + nsol, s->buf.d_gains, sizeof(double) * ngain, hipMemcpyDeviceToHost, s->lazy.aux_stream));
+  HIP_TRY(hipEventRecord(s->lazy.ev_pref, s->lazy.aux_stream));
   s->pref_b = b;
   s->pref_collapsed = false;
   return GAR_HIP_OK;
@@ -2142,7 +2004,7 @@ const double *gar_hip_host_results(gar_hip_solver *s, int64_t offs[3]) {
   }
   if (s->multi)
     return s->multi->h_results;
-  return s->h_results;
+  return s->buf.h_results;
 }
 
 int gar_hip_get_gains_all(gar_hip_solver *s, int b, double *ff_all, double *fb_all) {
@@ -2164,7 +2026,7 @@ static int get_value_dev(gar_hip_solver *s, int b, int t, double *Vxx, double *v
     return rc;
   const gar_stage_meta &m = s->meta[t];
   const gar_factor_offsets o = gar_factor_layout(m.nx, m.nu, m.nc, s->dense ? 2 * m.nx2 : m.nx2, m.nth);
-  const double *rec = s->d_fac + (int64_t)b * s->fac_doubles + m.fac_off;
+  const double *rec = s->buf.d_fac + (int64_t)b * s->fac_doubles + m.fac_off;
   std::vector<double> packed; // the serial one-wave family keeps the lower triangle, packed (gar_layout.h)
   int rc = 0;
   if (s->vxx_packed && Vxx) {
@@ -2198,30 +2060,28 @@ static int get_kkt_dev(gar_hip_solver *s, int b, int t, double mueq, double *out
   const int nk = m.nu + m.nc;
   if (nk == 0)
     return GAR_HIP_OK;
-  if ((int64_t)nk * nk > s->kkt_doubles) {
-    if (s->d_kkt)
-      (void)hipFree(s->d_kkt);
-    s->d_kkt = nullptr;
-    HIP_TRY(gar_dev_malloc((void **)&s->d_kkt, sizeof(double) * (size_t)nk * nk));
-    s->kkt_doubles = (int64_t)nk * nk;
+  if ((int64_t)nk * nk > s->buf.kkt_doubles) {
+    s->buf.kkt_doubles = 0;
+    HIP_TRY(s->buf.d_kkt.alloc((size_t)nk * nk)); // (lets the smaller one go first)
+    s->buf.kkt_doubles = (int64_t)nk * nk;
   }
   if (commit(s) != GAR_HIP_OK)
     return GAR_HIP_ERR_DEVICE;
   const int nth_st = (m.flags & GAR_KNOT_HAS_PARAM) ? m.nth : 0;
   const gar_knot_offsets ko = gar_knot_layout(m.nx, m.nu, m.nc, m.nx2, nth_st);
-  const double *knot = s->d_prob + (int64_t)b * s->prob_doubles + m.in_off;
+  const double *knot = s->buf.d_prob + (int64_t)b * s->prob_doubles + m.in_off;
   // the stage's value-function term: none at the terminal knot and at the last knot of a leg (each leg ends
   // with terminalSolve, parallel-solver.hxx:150-160)
   const double *Vn = nullptr;
   if (t < s->horizon && !(m.flags & GAR_KNOT_LEG_END) && m.nu > 0) {
     const gar_stage_meta &mn = s->meta[t + 1];
     const gar_factor_offsets fn = gar_factor_layout(mn.nx, mn.nu, mn.nc, mn.nx2, mn.nth);
-    Vn = s->d_fac + (int64_t)b * s->fac_doubles + mn.fac_off + fn.Vxx;
+    Vn = s->buf.d_fac + (int64_t)b * s->fac_doubles + mn.fac_off + fn.Vxx;
   }
   hipLaunchKernelGGL(gar::gar_kkt_matrix, dim3(1), dim3(256), 0, s->stream, knot, ko, Vn, m.nx2, m.nu, m.nc, mueq,
-                     s->d_kkt, s->vxx_packed ? 1 : 0, (s->qr_packed && t < s->horizon) ? 1 : 0);
+                     s->buf.d_kkt.get(), s->vxx_packed ? 1 : 0, (s->qr_packed && t < s->horizon) ? 1 : 0);
   HIP_TRY(hipGetLastError());
-  if (int rc = d2h(s, out, s->d_kkt, (int64_t)nk * nk))
+  if (int rc = d2h(s, out, s->buf.d_kkt, (int64_t)nk * nk))
     return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
   return GAR_HIP_OK;
@@ -2229,7 +2089,7 @@ static int get_kkt_dev(gar_hip_solver *s, int b, int t, double mueq, double *out
 
 static int get_initial_dev(gar_hip_solver *s, int b, double *kkt0_ff, double *kkt0_fth,
                         double *thGrad, double *thHess) {
-  const double *io = s->d_init + (int64_t)b * s->init_doubles;
+  const double *io = s->buf.d_init + (int64_t)b * s->init_doubles;
   const int64_t n0 = s->n0, nth = s->nth0;
   int rc = d2h(s, kkt0_ff, io, n0);
   rc |= d2h(s, kkt0_fth, io + n0, n0 * nth);
@@ -2247,16 +2107,14 @@ int gar_hip_debug_trace(gar_hip_solver *s, int enable, long long out[64]) {
     return fail(GAR_HIP_ERR_ARG, "null solver");
   GAR_MULTI(s, gar_hip_debug_trace(s->multi->subs[0], enable, out));
   HIP_TRY(hipStreamSynchronize(s->stream));
-  if (enable && !s->d_trace) {
-    HIP_TRY(gar_dev_malloc((void **)&s->d_trace, sizeof(long long) * 64));
-    HIP_TRY(hipMemset(s->d_trace, 0, sizeof(long long) * 64));
+  if (enable && !s->buf.d_trace) {
+    HIP_TRY(s->buf.d_trace.alloc(64));
+    HIP_TRY(hipMemset(s->buf.d_trace, 0, sizeof(long long) * 64));
   }
-  if (out && s->d_trace)
-    HIP_TRY(hipMemcpy(out, s->d_trace, sizeof(long long) * 64, hipMemcpyDeviceToHost));
-  if (!enable && s->d_trace) {
-    (void)hipFree(s->d_trace);
-    s->d_trace = nullptr;
-  }
+  if (out && s->buf.d_trace)
+    HIP_TRY(hipMemcpy(out, s->buf.d_trace, sizeof(long long) * 64, hipMemcpyDeviceToHost));
+  if (!enable)
+    s->buf.d_trace.reset();
   return GAR_HIP_OK;
 }
 
@@ -2283,20 +2141,20 @@ int gar_hip_update_lq_subproblem_device(gar_hip_solver *s, const double *deriv_d
   if (int rc = commit(s)) // pending host staging first; later host writes flush only their own ranges
     return rc;
   const gar::HostLayout &u = caller_layout(s); // the layout of the derivative buffer: the caller's dimensions
-  if (!s->d_deriv_off) {
-    HIP_TRY(gar_dev_malloc((void **)&s->d_deriv_off, sizeof(long long) * u.deriv_off.size()));
-    HIP_TRY(hipMemcpy(s->d_deriv_off, u.deriv_off.data(), sizeof(long long) * u.deriv_off.size(),
+  if (!s->buf.d_deriv_off) {
+    HIP_TRY(s->buf.d_deriv_off.alloc(u.deriv_off.size()));
+    HIP_TRY(hipMemcpy(s->buf.d_deriv_off, u.deriv_off.data(), sizeof(long long) * u.deriv_off.size(),
                       hipMemcpyHostToDevice));
   }
   gar::UpdateParams U{};
-  U.meta = s->d_meta;
+  U.meta = s->buf.d_meta;
   U.deriv = deriv_dev;
-  U.prob = s->d_prob;
+  U.prob = s->buf.d_prob;
   U.deriv_stride = u.deriv_doubles;
   U.prob_stride = s->prob_doubles;
   U.G0_off = s->G0_off;
   U.g0_off = s->g0_off;
-  U.deriv_off = s->d_deriv_off;
+  U.deriv_off = s->buf.d_deriv_off;
   U.d_G0 = u.d_G0;
   U.d_g0 = u.d_g0;
   U.d_iH = u.d_iH;
@@ -2326,7 +2184,7 @@ int gar_hip_download_packed(gar_hip_solver *s, int b0, int nb, double *packed) {
     const gar::HostLayout &u = *s->ulay;
     std::vector<double> dev((size_t)s->prob_doubles);
     for (int b = b0; b < b0 + nb; ++b) {
-      HIP_TRY(hipMemcpyAsync(dev.data(), s->d_prob + (int64_t)b * s->prob_doubles, sizeof(double) * dev.size(),
+      HIP_TRY(hipMemcpyAsync(dev.data(), s->buf.d_prob + (int64_t)b * s->prob_doubles, sizeof(double) * dev.size(),
                              hipMemcpyDeviceToHost, s->stream));
       HIP_TRY(hipStreamSynchronize(s->stream));
       double *rec = packed + (int64_t)(b - b0) * u.prob_doubles;
@@ -2359,7 +2217,7 @@ int gar_hip_download_packed(gar_hip_solver *s, int b0, int nb, double *packed) {
     }
     return GAR_HIP_OK;
   }
-  HIP_TRY(hipMemcpyAsync(packed, s->d_prob + (int64_t)b0 * s->prob_doubles,
+  HIP_TRY(hipMemcpyAsync(packed, s->buf.d_prob + (int64_t)b0 * s->prob_doubles,
                          sizeof(double) * (size_t)s->prob_doubles * nb, hipMemcpyDeviceToHost,
                          s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -2385,9 +2243,9 @@ int gar_hip_set_timing(gar_hip_solver *s, int enable) {
     return fail(GAR_HIP_ERR_ARG, "null solver");
   GAR_MULTI(s, multi_all(s, [&](gar_hip_solver *q) { return gar_hip_set_timing(q, enable); }));
   HIP_TRY(hipStreamSynchronize(s->stream));
-  if (enable && !s->ev[0])
-    for (auto &e : s->ev)
-      HIP_TRY(hipEventCreate(&e));
+  if (enable && !s->lazy.ev[0])
+    for (Event &e : s->lazy.ev)
+      HIP_TRY(e.create());
   s->timing = enable != 0;
   return GAR_HIP_OK;
 }
@@ -2405,18 +2263,18 @@ int gar_hip_last_kernel_ms(gar_hip_solver *s, double out[3]) {
   if (pipe_on(s)) { // per HALF-batch launch, the mean of the two halves; the initial stage rides inside the sweep
     out[0] = out[1] = out[2] = 0.0;
     for (int h = 0; h < 2; ++h) {
-      HIP_TRY(hipEventElapsedTime(&ms, s->pipe_evT[h][0], s->pipe_evT[h][1]));
+      HIP_TRY(hipEventElapsedTime(&ms, s->pipe.evT[h][0], s->pipe.evT[h][1]));
       out[0] += 0.5 * ms;
-      HIP_TRY(hipEventElapsedTime(&ms, s->pipe_evT[h][2], s->pipe_evT[h][3]));
+      HIP_TRY(hipEventElapsedTime(&ms, s->pipe.evT[h][2], s->pipe.evT[h][3]));
       out[2] += 0.5 * ms;
     }
     return GAR_HIP_OK;
   }
-  HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+  HIP_TRY(hipEventElapsedTime(&ms, s->lazy.ev[0], s->lazy.ev[1]));
   out[0] = ms;
-  HIP_TRY(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
+  HIP_TRY(hipEventElapsedTime(&ms, s->lazy.ev[1], s->lazy.ev[2]));
   out[1] = ms;
-  HIP_TRY(hipEventElapsedTime(&ms, s->ev[3], s->ev[4]));
+  HIP_TRY(hipEventElapsedTime(&ms, s->lazy.ev[3], s->lazy.ev[4]));
   out[2] = ms;
   return GAR_HIP_OK;
 }
@@ -2432,14 +2290,14 @@ int gar_hip_collapse_feedback(gar_hip_solver *s) {
     return GAR_HIP_OK; // no-op except Parallel (riccati-base.hpp:33)
   if (s->fold) { // the wave-leg family's own records (then re-expanded on request); flagged problems: generic records
     const int *flags = status_flags(s);
-    hipLaunchKernelGGL(s->leg_collapse_kernel, dim3((unsigned)s->batch), dim3(256), 0, s->stream, s->d_meta2, s->d_fac2,
+    hipLaunchKernelGGL(s->leg_collapse_kernel, dim3((unsigned)s->batch), dim3(256), 0, s->stream, s->buf.d_meta2.get(), s->buf.d_fac2.get(),
                        (long long)s->flay->fac_doubles, s->batch, flags, 0);
-    hipLaunchKernelGGL(gar::gar_collapse_feedback, dim3((unsigned)s->batch), dim3(256), 0, s->stream, s->d_meta, s->d_fac,
+    hipLaunchKernelGGL(gar::gar_collapse_feedback, dim3((unsigned)s->batch), dim3(256), 0, s->stream, s->buf.d_meta.get(), s->buf.d_fac.get(),
                        (long long)s->fac_doubles, s->batch, flags, 1);
-    s->fold_expanded = false;
+    s->buf.fold_expanded = false;
   } else {
     hipLaunchKernelGGL(s->leg_collapse_kernel ? s->leg_collapse_kernel : gar::gar_collapse_feedback,
-                       dim3((unsigned)s->batch), dim3(256), 0, s->stream, s->d_meta, s->d_fac,
+                       dim3((unsigned)s->batch), dim3(256), 0, s->stream, s->buf.d_meta.get(), s->buf.d_fac.get(),
                        (long long)s->fac_doubles, s->batch, (const int *)nullptr, 0);
   }
   HIP_TRY(hipGetLastError());
@@ -2451,8 +2309,8 @@ int gar_hip_cycle_append(gar_hip_solver *s, const int32_t d[5]) {
   if (!s || !d)
     return fail(GAR_HIP_ERR_ARG, "bad argument");
   GAR_MULTI(s, multi_cycle_append(s, d));
-  if (s->ev_pref)
-    HIP_TRY(hipEventSynchronize(s->ev_pref));
+  if (s->lazy.ev_pref)
+    HIP_TRY(hipEventSynchronize(s->lazy.ev_pref));
   s->pref_b = -1;
   s->eager_fwd = false;
   const int N = s->horizon;
@@ -2486,7 +2344,7 @@ int gar_hip_cycle_append(gar_hip_solver *s, const int32_t d[5]) {
       s->meta[t].in_off = s->uni_in0 + p * s->uni_in_rec;
       s->meta[t].fac_off = p * s->uni_fac_rec;
     }
-    HIP_TRY(hipMemcpyAsync(s->d_meta, s->meta.data(), sizeof(gar_stage_meta) * s->meta.size(),
+    HIP_TRY(hipMemcpyAsync(s->buf.d_meta, s->meta.data(), sizeof(gar_stage_meta) * s->meta.size(),
                            hipMemcpyHostToDevice, s->stream));
     if (s->serial_fold) { // the folded layout turns with the caller's: the family's records stay where they are too
       gar::HostLayout &f = *s->flay;
@@ -2496,16 +2354,16 @@ int gar_hip_cycle_append(gar_hip_solver *s, const int32_t d[5]) {
         f.meta[t].in_off = f.uni_in0 + p * f.uni_in_rec;
         f.meta[t].fac_off = p * f.uni_fac_rec;
       }
-      HIP_TRY(hipMemcpyAsync(s->d_meta2, f.meta.data(), sizeof(gar_stage_meta) * f.meta.size(), hipMemcpyHostToDevice,
+      HIP_TRY(hipMemcpyAsync(s->buf.d_meta2, f.meta.data(), sizeof(gar_stage_meta) * f.meta.size(), hipMemcpyHostToDevice,
                              s->stream));
-      HIP_TRY(hipMemset2DAsync(s->d_fac2 + f.meta[N - 1].fac_off, sizeof(double) * (size_t)f.fac_doubles, 0,
+      HIP_TRY(hipMemset2DAsync(s->buf.d_fac2 + f.meta[N - 1].fac_off, sizeof(double) * (size_t)f.fac_doubles, 0,
                                sizeof(double) * (size_t)f.uni_fac_rec, (size_t)s->batch, s->stream));
-      s->fold_expanded = false;
+      s->buf.fold_expanded = false;
     }
-    HIP_TRY(hipMemsetAsync(s->d_init, 0, sizeof(double) * (size_t)s->init_doubles * s->batch, s->stream));
+    HIP_TRY(hipMemsetAsync(s->buf.d_init, 0, sizeof(double) * (size_t)s->init_doubles * s->batch, s->stream));
     // the last-but-one factor is re-created (zero) like the reference's StageFactor (:84-85): one
     // strided memset over the batch, asynchronous
-    HIP_TRY(hipMemset2DAsync(s->d_fac + s->meta[N - 1].fac_off, sizeof(double) * (size_t)s->fac_doubles, 0,
+    HIP_TRY(hipMemset2DAsync(s->buf.d_fac + s->meta[N - 1].fac_off, sizeof(double) * (size_t)s->fac_doubles, 0,
                              sizeof(double) * (size_t)s->uni_fac_rec, (size_t)s->batch, s->stream));
     if (s->padded) { // the slot's dummy diagonals (Q = I, R = I on the padded part) are part of the knot the caller
       // uploads next through gar_hip_upload_stage, which writes whole padded blocks: nothing to do here
@@ -2532,15 +2390,14 @@ int gar_hip_cycle_append(gar_hip_solver *s, const int32_t d[5]) {
       return rc; // g_last_error says why
   }
   HIP_TRY(hipStreamSynchronize(s->stream));
-  free_device(s);
-  s->staged = s->dirty = false;
+  s->buf = {}; // (every buffer of the old layout, the lazily created ones included)
   s->user_dims5 = nd;
   // the pipelined schedule belongs to the kernel family that was bound: it is re-validated against the new one (its
   // half streams and events are kept), and silently off when the new shape has no such family
   const int wanted = s->pipe_requested; // 2: the caller's explicit wish; -1: the library's own choice; 0: off
   s->pipe_halves = 0;
-  s->pipe_forked = false;
-  s->pipe_evB_valid[0] = s->pipe_evB_valid[1] = false;
+  s->pipe.forked = false;
+  s->pipe.evB_valid[0] = s->pipe.evB_valid[1] = false;
   if (int rc = configure(s))
     return rc;
   if (int rc = allocate(s))

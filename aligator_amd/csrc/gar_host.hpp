@@ -1,9 +1,11 @@
-// gar_host.hpp -- the two parts of the solver handle (gar_hip.cpp: gar_hip_solver derives from both) that are not run
-// state: the record layout of one problem (HostLayout: build_layout fills it; the caller-facing and the scratch
-// layouts of a solver are bare ones) and the kernel family bound to it (KernelBinding: select_kernel resets it by value
-// and the bind_* functions of gar_select.hpp fill it).  Included by gar_hip.cpp behind its standard headers (<cstdlib>,
-// <cstring>, <map>, <mutex>, <string>, <vector>: none is included here) and the kernel headers; internal linkage, like
-// the rest of that unit's host code.  Ahead of them: gar_option and its two predicates, which need nothing of a solver.
+// gar_host.hpp -- what the solver handle (gar_hip.cpp: gar_hip_solver) is made of, apart from its settings: the record
+// layout of one problem (HostLayout: build_layout fills it; the caller-facing and the scratch layouts of a solver are
+// bare ones), the kernel family bound to it (KernelBinding: select_kernel resets it by value and the bind_* functions of
+// gar_select.hpp fill it) and the run state, grouped by lifetime (LayoutState, PipeState, LazyState) and held in the
+// four move-only owners below.  Included by gar_hip.cpp behind <hip/hip_runtime.h>, its standard headers (<atomic>,
+// <cstdlib>, <cstring>, <map>, <mutex>, <string>, <utility>, <vector>: none is included here) and the kernel headers;
+// internal linkage, like the rest of that unit's host code.  Ahead of them: gar_option and its two predicates, which
+// need nothing of a solver.
 #pragma once
 
 namespace {
@@ -40,6 +42,77 @@ inline bool option_is(const char *name, const char *word) {
   const char *v = gar_option(name);
   return v && std::strcmp(v, word) == 0;
 }
+// ---- owners -----------------------------------------------------------------------------------------------------
+// Every device buffer, pinned host buffer, stream and event of the library is held by one of the four owners below:
+// move-only, released by reset() or the destructor, read through get() or the implicit conversion to the raw handle.
+// Nothing else: no size, no reference count -- a caller that needs the size keeps it (kkt_doubles beside d_kkt).
+template <class H, class Arg, hipError_t (*Release)(Arg)> struct Owner {
+  Owner() = default;
+  Owner(Owner &&o) noexcept : h(std::exchange(o.h, nullptr)) {}
+  Owner &operator=(Owner &&o) noexcept {
+    if (this != &o) {
+      reset();
+      h = std::exchange(o.h, nullptr);
+    }
+    return *this;
+  }
+  ~Owner() { reset(); }
+  void reset() {
+    if (h)
+      (void)Release(h);
+    h = nullptr;
+  }
+  H get() const { return h; }
+  operator H() const { return h; }
+
+protected:
+  H h = nullptr;
+};
+
+// Every device / pinned-host allocation goes through the two buffer owners and is counted
+// (gar_hip_debug_alloc_count): the reference runs backward / forward under ALIGATOR_NOMALLOC_SCOPED
+// (gar/proximal-riccati.hxx:35, tests/nomalloc.cpp); tests/test_nomalloc.py asserts the same here -- the count
+// does not move across repeated backward + forward calls.
+std::atomic<long long> g_alloc_count{0};
+
+template <class T> struct DevBuf : Owner<T *, void *, hipFree> { // n: elements of T
+  hipError_t alloc(size_t n) {
+    this->reset();
+    g_alloc_count.fetch_add(1, std::memory_order_relaxed);
+    return hipMalloc((void **)&this->h, sizeof(T) * n);
+  }
+  hipError_t zalloc(size_t n) {
+    const hipError_t e = alloc(n);
+    return e != hipSuccess ? e : hipMemset(this->h, 0, sizeof(T) * n);
+  }
+};
+template <class T> struct PinnedBuf : Owner<T *, void *, hipHostFree> {
+  hipError_t alloc(size_t n, unsigned flags) {
+    this->reset();
+    g_alloc_count.fetch_add(1, std::memory_order_relaxed);
+    return hipHostMalloc((void **)&this->h, sizeof(T) * n, flags);
+  }
+};
+struct Stream : Owner<hipStream_t, hipStream_t, hipStreamDestroy> {
+  hipError_t create(unsigned flags) {
+    reset();
+    return hipStreamCreateWithFlags(&h, flags);
+  }
+  hipError_t create_with_priority(unsigned flags, int priority) {
+    reset();
+    return hipStreamCreateWithPriority(&h, flags, priority);
+  }
+};
+struct Event : Owner<hipEvent_t, hipEvent_t, hipEventDestroy> {
+  hipError_t create() { // (with timing)
+    reset();
+    return hipEventCreate(&h);
+  }
+  hipError_t create(unsigned flags) {
+    reset();
+    return hipEventCreateWithFlags(&h, flags);
+  }
+};
 } // namespace
 
 namespace gar {
@@ -135,6 +208,72 @@ struct KernelBinding {
   bool serial_fold = false;
   bool serial_fold_fallback = false; // the any-dimension kernels fit a CU's LDS: they take the flagged problems
   bool sf_fb_t2 = false, sf_vxx_packed = false, sf_qr_packed = false;
+};
+
+// ---- run state, by lifetime ---------------------------------------------------------------------------------------
+// Layout lifetime: built by allocate() or, member by member, on an entry point's first use; dropped as one value
+// (`s->buf = {}`, behind a stream synchronisation) when gar_hip_cycle_append changes the dimensions, and with the solver.
+struct LayoutState {
+  DevBuf<gar_stage_meta> d_meta;
+  DevBuf<double> d_prob, d_fac, d_sol, d_init, d_theta;
+  DevBuf<int> d_status;
+  DevBuf<double> d_kkt; // gar_hip_get_kkt's staging ((nu+nc)^2 doubles, allocated on first use)
+  int64_t kkt_doubles = 0;
+  // `flay`'s device records (gar_hip_solver::flay: the folded problem or the segment legs' scratch records)
+  DevBuf<double> d_prob2, d_fac2;
+  DevBuf<gar_stage_meta> d_meta2;
+  DevBuf<int> d_cseg_resume;
+  bool fold_expanded = false, coupled_known = false;
+  std::vector<int> h_coupled;
+  // leg mode: this rank's boundary tuples and, when the legs are sharded over ranks (world > 1), the buffer every
+  // rank's tuples are gathered into -- with one rank the local buffer IS the gathered one (bound_all)
+  DevBuf<double> d_bound_local, d_bound_gathered, d_csol, d_cscratch;
+  double *bound_all() const { return d_bound_gathered ? d_bound_gathered.get() : d_bound_local.get(); }
+  // host staging
+  PinnedBuf<double> h_prob; // batch * prob_doubles (when small enough)
+  bool staged = false, dirty = false;
+  bool stage_nt = false; // pack with non-temporal stores (problems of >= 12 MiB; GAR_HIP_STAGE_NT=0/1 overrides)
+  // what the host wrote into the staging area since the last flush: per problem, a sorted list of
+  // disjoint [lo, hi) ranges (doubles).  commit() copies exactly these, so knots a device-resident
+  // producer wrote in place (gar_hip_device_problems) survive a later set_init / upload_stage
+  std::vector<std::vector<std::pair<int64_t, int64_t>>> dirty_iv;
+  DevBuf<long long> d_trace;     // 64 cycle stamps (debug)
+  DevBuf<long long> d_deriv_off; // device-resident updateLQSubproblem: HostLayout::deriv_off on the device
+  // bulk read-back (gar_hip_fetch_results): HostLayout::gain_off on the device, the device gather buffer and the
+  // pinned host buffer [solution | ff_all | fb_all] of one problem
+  DevBuf<long long> d_gain_off;
+  DevBuf<double> d_gains;
+  PinnedBuf<double> h_results;
+};
+
+// Solver lifetime: the pipelined sweep's half streams and events (gar_hip_set_pipeline; the serial one-wave family,
+// batch >= 2), created as one group on the first request that is served; they survive a rebuild and die with the solver.
+// The batch is cut in two halves with a stream each; backward sweeps alternate between the halves (events), the
+// forward sweep of a half is gar_forward_lean, which fits in the registers and the LDS the backward wave of the
+// OTHER half leaves free on every SIMD (gar_forward_lean.hpp): B(h0) | F(h0) + B(h1) | F(h1) + B'(h0) | ...
+struct PipeState {
+  Stream stream[2];
+  Event evB[2], evF[2], evFork;
+  Event evT[2][4]; // timing
+  bool evB_valid[2] = {false, false};
+  bool forked = false; // the half streams hold work the caller's stream has not been ordered behind
+};
+
+// Solver lifetime: what three entry points create on first use, each group whole or not at all; they survive a rebuild
+// and die with the solver.
+struct LazyState {
+  // gar_hip_prefetch_gains: the bulk read-back of the gains started right behind the backward sweep on a second
+  // stream, so that it overlaps the forward sweep and the solution read-back
+  Stream aux_stream;
+  Event ev_main, ev_pref;
+  // gar_hip_backward_blocks on a problem without parameter: the roll-out and the solution's copy are enqueued BEHIND the
+  // sweep before the host waits for the status word, so that gar_hip_forward / the solution fetch find them done
+  PinnedBuf<int> h_status;
+  Event ev_status, ev_sol;
+  // gar_hip_set_timing: per-kernel timing of the sweep (bench.py's roofline figure): HIP events recorded on
+  // the launch stream around the backward sweep kernel, the initial-stage kernel and the forward
+  // sweep kernel of the LAST backward/forward calls
+  Event ev[5];
 };
 
 } // namespace

@@ -6,7 +6,7 @@
 
 // the timing API's event i (gar_hip_set_timing) on the launch stream; nothing unless timing is on (and `when`)
 inline hipError_t stamp(gar_hip_solver *s, int i, bool when = true) {
-  return s->timing && when ? hipEventRecord(s->ev[i], s->stream) : hipSuccess;
+  return s->timing && when ? hipEventRecord(s->lazy.ev[i], s->stream) : hipSuccess;
 }
 
 // MfmaParams of a stage sweep over the caller's knots: mfma_common + where the factor records go, mueq and the
@@ -15,7 +15,7 @@ inline hipError_t stamp(gar_hip_solver *s, int i, bool when = true) {
 // purpose -- a leg has no fused initial stage, no ring and no trace.  make_mfma_params adds them for the serial sweeps.
 gar::MfmaParams make_mfma_scratch_params(gar_hip_solver *s, double mueq, double *fac, long long fac_stride,
                                          long long fac_rec, long long fac_offN, int *resume) {
-  gar::MfmaParams M = mfma_common(s, *s, s->d_prob, fac, fac_stride);
+  gar::MfmaParams M = mfma_common(s, *s, s->buf.d_prob, fac, fac_stride);
   M.resume = resume;
   M.fac_rec = fac_rec;
   M.fac_offN = fac_offN;
@@ -27,17 +27,17 @@ gar::MfmaParams make_mfma_scratch_params(gar_hip_solver *s, double mueq, double 
 gar::MfmaParams make_mfma_params(gar_hip_solver *s, double mueq) {
   // (a serial-fold solver: the family sweeps the folded knots into its own records; the flags belong to the fold)
   const gar::HostLayout &L = s->serial_fold ? *s->flay : static_cast<const gar::HostLayout &>(*s);
-  gar::MfmaParams M = make_mfma_scratch_params(s, mueq, s->serial_fold ? s->d_fac2 : s->d_fac, L.fac_doubles, L.uni_fac_rec,
+  gar::MfmaParams M = make_mfma_scratch_params(s, mueq, s->serial_fold ? s->buf.d_fac2 : s->buf.d_fac, L.fac_doubles, L.uni_fac_rec,
                                                L.meta[s->horizon].fac_off, s->serial_fold ? nullptr : status_flags(s));
   if (s->serial_fold) {
-    M.prob = s->d_prob2;
+    M.prob = s->buf.d_prob2;
     M.prob_stride = L.prob_doubles;
     M.in_off0 = L.uni_in0;
     M.in_rec = L.uni_in_rec;
     M.in_offN = L.meta[s->horizon].in_off;
   }
-  M.trace = s->d_trace;
-  M.init = s->wave_kernel && s->wave_fused_init ? s->d_init : nullptr;
+  M.trace = s->buf.d_trace;
+  M.init = s->wave_kernel && s->wave_fused_init ? s->buf.d_init : nullptr;
   M.init_stride = s->init_doubles;
   M.G0_off = s->G0_off;
   M.g0_off = s->g0_off;
@@ -61,13 +61,13 @@ struct LegChunk {
 // the parameter recursion of the segment legs and of the constrained segment legs (which set `only`)
 gar::LegParamParams make_leg_param_params(gar_hip_solver *s, const LegChunk &c) {
   gar::LegParamParams Q{};
-  Q.meta = s->d_meta;
-  Q.meta2 = s->d_meta2;
-  Q.prob = s->d_prob;
-  Q.fac2 = s->d_fac2;
-  Q.fac = s->d_fac;
-  Q.boundary = s->d_bound_local + c.tup_shift;
-  Q.status = s->d_status;
+  Q.meta = s->buf.d_meta;
+  Q.meta2 = s->buf.d_meta2;
+  Q.prob = s->buf.d_prob;
+  Q.fac2 = s->buf.d_fac2;
+  Q.fac = s->buf.d_fac;
+  Q.boundary = s->buf.d_bound_local + c.tup_shift;
+  Q.status = s->buf.d_status;
   Q.prob_stride = s->prob_doubles;
   Q.fac_stride = s->fac_doubles;
   Q.fac2_stride = s->flay->fac_doubles;
@@ -85,11 +85,11 @@ gar::LegParamParams make_leg_param_params(gar_hip_solver *s, const LegChunk &c) 
 
 gar::CsegParams make_cseg_params(gar_hip_solver *s, double mueq, const LegChunk &c) {
   gar::CsegParams Cp{};
-  Cp.meta = s->d_meta;
-  Cp.prob = s->d_prob;
-  Cp.fac2 = s->d_fac2;
-  Cp.fac = s->d_fac;
-  Cp.status = s->d_status;
+  Cp.meta = s->buf.d_meta;
+  Cp.prob = s->buf.d_prob;
+  Cp.fac2 = s->buf.d_fac2;
+  Cp.fac = s->buf.d_fac;
+  Cp.status = s->buf.d_status;
   Cp.only = status_flags(s);
   Cp.prob_stride = s->prob_doubles;
   Cp.fac_stride = s->fac_doubles;
@@ -106,10 +106,10 @@ gar::CsegParams make_cseg_params(gar_hip_solver *s, double mueq, const LegChunk 
 
 gar::CsegFwdParams make_cseg_fwd_params(gar_hip_solver *s) {
   gar::CsegFwdParams F{};
-  F.meta = s->d_meta;
-  F.fac = s->d_fac;
-  F.sol = s->d_sol;
-  F.csol = s->d_csol;
+  F.meta = s->buf.d_meta;
+  F.fac = s->buf.d_fac;
+  F.sol = s->buf.d_sol;
+  F.csol = s->buf.d_csol;
   F.only = status_flags(s);
   F.fac_stride = s->fac_doubles;
   F.sol_stride = s->sol_doubles;
@@ -128,8 +128,8 @@ void backward_cstr_seg_legs(gar_hip_solver *s, double mueq, const LegChunk &c) {
   const dim3 grid = c.grid(s);
   const int *flagged = status_flags(s);
   const int N = s->horizon, l0 = c.l0;
-  const gar::MfmaParams M = make_mfma_scratch_params(s, mueq, s->d_fac2, s->flay->fac_doubles, s->cseg.rec,
-                                                     (long long)N * s->cseg.rec, s->d_cseg_resume);
+  const gar::MfmaParams M = make_mfma_scratch_params(s, mueq, s->buf.d_fac2, s->flay->fac_doubles, s->cseg.rec,
+                                                     (long long)N * s->cseg.rec, s->buf.d_cseg_resume);
   // (gar_cstr_seg.hpp) the leg-end stages -- V' = 0: no MFMA work, and the matrix on which Bunch-Kaufman pivots -- by a
   // workgroup each, then the chain once, leg by leg, from the knot below: decoupled -> coupled -> LDS Bunch-Kaufman;
   // CSTR_SEG_LEG_END = 0: the leg ends through the chain too, which then runs in two rounds -- coupled stage and LDS
@@ -176,7 +176,7 @@ int backward_wave_legs(gar_hip_solver *s, double mueq, const LegChunk &c) {
   HIP_TRY(stamp(s, 0, c.first));
   if (s->fold) { // knots with nc > 0: fold C, d into Q, q (gar_fold.hpp); problems with D != 0 get flagged
     s->fold_mueq = mueq;
-    s->fold_expanded = s->coupled_known = false;
+    s->buf.fold_expanded = s->buf.coupled_known = false;
     hipLaunchKernelGGL(gar::gar_fold_constraints, dim3((unsigned)(s->horizon + 1), (unsigned)s->batch), dim3(256),
                        fold_lds_bytes(s), s->stream, make_fold_params(s));
   }
@@ -196,7 +196,7 @@ int backward_wave_legs(gar_hip_solver *s, double mueq, const LegChunk &c) {
 int backward_seg_legs(gar_hip_solver *s, double mueq, const LegChunk &c) {
   const gar::HostLayout &f = *s->flay;
   const int N = s->horizon;
-  const gar::MfmaParams M = make_mfma_scratch_params(s, mueq, s->d_fac2, f.fac_doubles, f.uni_fac_rec, f.meta[N].fac_off,
+  const gar::MfmaParams M = make_mfma_scratch_params(s, mueq, s->buf.d_fac2, f.fac_doubles, f.uni_fac_rec, f.meta[N].fac_off,
                                                      status_flags(s));
   const dim3 grid = c.grid(s);
   HIP_TRY(stamp(s, 0, c.first));
@@ -218,8 +218,8 @@ int backward_seg_legs(gar_hip_solver *s, double mueq, const LegChunk &c) {
 // the any-dimension kernels' view of a serial-fold solver's folded records: the stand-alone initial stage of the family
 gar::GenericParams make_folded_params(gar_hip_solver *s, double mueq) {
   gar::GenericParams P = make_params(s, mueq);
-  P.meta = s->d_meta2;
-  P.fac = s->d_fac2;
+  P.meta = s->buf.d_meta2;
+  P.fac = s->buf.d_fac2;
   P.fac_stride = s->flay->fac_doubles;
   P.vxx_packed = s->sf_vxx_packed ? 1 : 0;
   return P;
@@ -231,7 +231,7 @@ int backward_serial(gar_hip_solver *s, double mueq) {
   HIP_TRY(stamp(s, 0));
   if (s->serial_fold) { // knots with nc > 0: fold C, d into Q, q in the family's knot format; problems with D != 0 get flagged
     s->fold_mueq = mueq;
-    s->fold_expanded = s->coupled_known = false;
+    s->buf.fold_expanded = s->buf.coupled_known = false;
     hipLaunchKernelGGL(gar::gar_fold_serial, dim3((unsigned)(s->horizon + 1), (unsigned)s->batch), dim3(256),
                        fold_lds_bytes(s), s->stream, make_serial_fold_params(s));
   }
@@ -314,9 +314,9 @@ gar::MfmaFwdParams make_mfma_fwd_params(gar_hip_solver *s) {
   gar::MfmaFwdParams F{};
   const int N = s->horizon;
   const gar::HostLayout &L = s->serial_fold ? *s->flay : static_cast<const gar::HostLayout &>(*s); // (the family's own records)
-  F.fac = s->serial_fold ? s->d_fac2 : s->d_fac;
-  F.init = s->d_init;
-  F.sol = s->d_sol;
+  F.fac = s->serial_fold ? s->buf.d_fac2 : s->buf.d_fac;
+  F.init = s->buf.d_init;
+  F.sol = s->buf.d_sol;
   F.fac_stride = L.fac_doubles;
   F.init_stride = s->init_doubles;
   F.sol_stride = s->sol_doubles;
@@ -419,11 +419,11 @@ int launch_forward(gar_hip_solver *s, const double *theta_dev) {
 
 gar::CondensedParams make_condensed_params(gar_hip_solver *s) {
   gar::CondensedParams C{};
-  C.ball = s->d_bound_all;
-  C.prob = s->d_prob;
-  C.scratch = s->d_cscratch;
-  C.csol = s->d_csol;
-  C.status = s->d_status;
+  C.ball = s->buf.bound_all();
+  C.prob = s->buf.d_prob;
+  C.scratch = s->buf.d_cscratch;
+  C.csol = s->buf.d_csol;
+  C.status = s->buf.d_status;
   C.prob_stride = s->prob_doubles;
   C.scratch_stride = s->cscratch_doubles;
   C.G0_off = s->G0_off;
@@ -439,7 +439,7 @@ gar::CondensedParams make_condensed_params(gar_hip_solver *s) {
   C.max_refinement = s->max_refinement;
   C.threshold = s->cond_threshold;
   C.backward_ok = s->cond_backward_ok;
-  C.trace = s->d_trace;
+  C.trace = s->buf.d_trace;
   C.gated = 0;
   return C;
 }

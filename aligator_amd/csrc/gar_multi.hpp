@@ -48,13 +48,13 @@ __global__ void __launch_bounds__(256) gar_multi_gather(MultiGatherParams P) {
 
 struct gar_multi {
   std::vector<gar_hip_solver *> subs; // subs[r]: the ranked solver of device r (rank r of world W)
-  std::vector<hipEvent_t> ev_legs;    // device r's leg sweep of the current backward is done
-  std::vector<hipEvent_t> ev_gath;    // device r has read every peer's tuples of the current backward
+  std::vector<Event> ev_legs;         // device r's leg sweep of the current backward is done
+  std::vector<Event> ev_gath;         // device r has read every peer's tuples of the current backward
   std::vector<int> t_lo, t_hi;        // stages [t_lo, t_hi) live on device r
   std::vector<int> owner;             // per stage
   bool pull = false;                  // exchange: one gather kernel per device over peer-mapped buffers
   bool swept = false;
-  double *h_results = nullptr;        // pinned, merged [solution | ff_all | fb_all] of one problem
+  PinnedBuf<double> h_results;        // merged [solution | ff_all | fb_all] of one problem (portable: every device writes it)
 };
 
 namespace {
@@ -91,15 +91,11 @@ void multi_destroy(gar_hip_solver *s) {
     {
       DeviceGuard g(M->subs[r]->device);
       (void)hipStreamSynchronize(M->subs[r]->stream);
-      if (r < M->ev_legs.size() && M->ev_legs[r])
-        (void)hipEventDestroy(M->ev_legs[r]);
-      if (r < M->ev_gath.size() && M->ev_gath[r])
-        (void)hipEventDestroy(M->ev_gath[r]);
+      M->ev_legs[r].reset(); // (its two events, on the device they were made on)
+      M->ev_gath[r].reset();
     }
     gar_hip_solver_destroy(M->subs[r]);
   }
-  if (M->h_results)
-    (void)hipHostFree(M->h_results);
   delete M;
   s->multi = nullptr;
   delete s;
@@ -119,15 +115,15 @@ int upload_packed_range(gar_hip_solver *q, int b0, int nb, const double *packed,
   const int64_t P = q->prob_doubles;
   for (int b = b0; b < b0 + nb; ++b) {
     const double *src = packed + (int64_t)(b - b0) * P + lo;
-    if (q->staged) {
-      std::memcpy(q->h_prob + (int64_t)b * P + lo, src, sizeof(double) * (size_t)(hi - lo));
+    if (q->buf.staged) {
+      std::memcpy(q->buf.h_prob + (int64_t)b * P + lo, src, sizeof(double) * (size_t)(hi - lo));
       mark_dirty(q, b, lo, hi);
     } else {
-      HIP_TRY(hipMemcpyAsync(q->d_prob + (int64_t)b * P + lo, src, sizeof(double) * (size_t)(hi - lo),
+      HIP_TRY(hipMemcpyAsync(q->buf.d_prob + (int64_t)b * P + lo, src, sizeof(double) * (size_t)(hi - lo),
                              hipMemcpyHostToDevice, q->stream));
     }
   }
-  if (!q->staged)
+  if (!q->buf.staged)
     HIP_TRY(hipStreamSynchronize(q->stream));
   return GAR_HIP_OK;
 }
@@ -220,16 +216,16 @@ int multi_exchange_and_condensed(gar_hip_solver *s) {
     if (M->pull) { // ONE kernel: W chunks read (W-1 of them over xGMI), written into this device's gathered buffer
       gar::MultiGatherParams P{};
       for (size_t p = 0; p < W; ++p)
-        P.src[p] = M->subs[p]->d_bound_local;
-      P.dst = q->d_bound_all;
+        P.src[p] = M->subs[p]->buf.d_bound_local;
+      P.dst = q->buf.bound_all();
       P.chunk = chunk;
       const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>(64, (chunk + 255) / 256));
       hipLaunchKernelGGL(gar::gar_multi_gather, dim3(blocks, (unsigned)W), dim3(256), 0, q->stream, P);
       HIP_TRY(hipGetLastError());
     } else {
       for (size_t p = 0; p < W; ++p) {
-        double *dst = q->d_bound_all + (long long)p * chunk;
-        const double *src = M->subs[p]->d_bound_local;
+        double *dst = q->buf.bound_all() + (long long)p * chunk;
+        const double *src = M->subs[p]->buf.d_bound_local;
         if (M->subs[p]->device == q->device)
           HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)chunk, hipMemcpyDeviceToDevice, q->stream));
         else
@@ -264,7 +260,7 @@ int multi_num_failed(gar_hip_solver *s) {
   std::vector<int> acc((size_t)s->batch, 0), st((size_t)s->batch);
   for (gar_hip_solver *q : s->multi->subs) {
     DeviceGuard g(q->device);
-    if (hipMemcpyAsync(st.data(), q->d_status, sizeof(int) * st.size(), hipMemcpyDeviceToHost, q->stream) != hipSuccess ||
+    if (hipMemcpyAsync(st.data(), q->buf.d_status, sizeof(int) * st.size(), hipMemcpyDeviceToHost, q->stream) != hipSuccess ||
         hipStreamSynchronize(q->stream) != hipSuccess)
       return -1;
     for (size_t i = 0; i < st.size(); ++i)
@@ -345,12 +341,12 @@ int multi_fetch_results(gar_hip_solver *s, int b, int what) {
   const gar::HostLayout &L = caller_layout(s);
   const size_t nsol = (size_t)L.sol_doubles, ngain = (size_t)(L.ff_all_doubles + L.fb_all_doubles);
   if (!M->h_results) {
-    double *h = nullptr;
-    const hipError_t e = gar_host_malloc((void **)&h, sizeof(double) * (nsol + ngain), hipHostMallocPortable);
+    PinnedBuf<double> h;
+    const hipError_t e = h.alloc(nsol + ngain, hipHostMallocPortable);
     if (e != hipSuccess)
       return fail(GAR_HIP_ERR_DEVICE, std::string("gar_hip_fetch_results: ") + hipGetErrorString(e));
     std::memset(h, 0, sizeof(double) * (nsol + ngain));
-    M->h_results = h;
+    M->h_results = std::move(h);
   }
   // every device gathers and copies its own stages only, all devices at once; then one wait per device
   for (size_t r = 0; r < M->subs.size(); ++r) {
@@ -364,9 +360,9 @@ int multi_fetch_results(gar_hip_solver *s, int b, int what) {
     for (size_t r = 0; r < M->subs.size(); ++r) {
       gar_hip_solver *q = M->subs[r];
       if (q->padded)
-        strip_solution_rec(q, q->h_results + nsol + ngain, q->h_results);
+        strip_solution_rec(q, q->buf.h_results + nsol + ngain, q->buf.h_results);
       const SolRange R = multi_sol_range(s, r);
-      const double *src = q->h_results;
+      const double *src = q->buf.h_results;
       double *dst = M->h_results;
       std::copy(src + L.sol_x + R.x0, src + L.sol_x + R.x1, dst + L.sol_x + R.x0);
       std::copy(src + L.sol_u + R.u0, src + L.sol_u + R.u1, dst + L.sol_u + R.u0);
@@ -397,9 +393,7 @@ int multi_cycle_append(gar_hip_solver *s, const int32_t d[5]) {
   if (int rc = configure(s))
     return rc;
   multi_ranges(s);
-  if (M->h_results) // the merged record's size follows the layout
-    (void)hipHostFree(M->h_results);
-  M->h_results = nullptr;
+  M->h_results.reset(); // the merged record's size follows the layout
   M->swept = false;
   return GAR_HIP_OK;
 }
@@ -462,8 +456,8 @@ gar_hip_solver *multi_create(int ndev, const int *dev_ids, int horizon, const in
   normalise_terminal(s);
   gar_multi *M = s->multi;
   M->subs.assign((size_t)ndev, nullptr);
-  M->ev_legs.assign((size_t)ndev, nullptr);
-  M->ev_gath.assign((size_t)ndev, nullptr);
+  M->ev_legs.resize((size_t)ndev);
+  M->ev_gath.resize((size_t)ndev);
   if (configure(s) != GAR_HIP_OK) { // the layout only: this object owns no device memory
     multi_destroy(s);
     return nullptr;
@@ -477,8 +471,8 @@ gar_hip_solver *multi_create(int ndev, const int *dev_ids, int horizon, const in
       return nullptr;
     }
     DeviceGuard g(dev_ids[r]);
-    if (hipEventCreateWithFlags(&M->ev_legs[(size_t)r], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&M->ev_gath[(size_t)r], hipEventDisableTiming) != hipSuccess) {
+    if (M->ev_legs[(size_t)r].create(hipEventDisableTiming) != hipSuccess ||
+        M->ev_gath[(size_t)r].create(hipEventDisableTiming) != hipSuccess) {
       multi_destroy(s);
       fail(GAR_HIP_ERR_DEVICE, "hipEventCreate failed");
       return nullptr;

@@ -31,17 +31,17 @@ inline void pipe_range(const gar_hip_solver *s, int h, int *b0, int *nb) {
 }
 // the caller's stream behind everything the half streams hold
 int pipe_join(gar_hip_solver *s) {
-  if (!s->pipe_forked)
+  if (!s->pipe.forked)
     return GAR_HIP_OK;
   for (int h = 0; h < 2; ++h) {
-    HIP_TRY(hipEventRecord(s->pipe_evF[h], s->pipe_stream[h])); // (covers the sweeps too: stream order)
-    HIP_TRY(hipStreamWaitEvent(s->stream, s->pipe_evF[h], 0));
+    HIP_TRY(hipEventRecord(s->pipe.evF[h], s->pipe.stream[h])); // (covers the sweeps too: stream order)
+    HIP_TRY(hipStreamWaitEvent(s->stream, s->pipe.evF[h], 0));
   }
-  s->pipe_forked = false;
+  s->pipe.forked = false;
   return GAR_HIP_OK;
 }
 void pipe_autojoin(const gar_hip_solver *s) {
-  if (s && s->pipe_forked)
+  if (s && s->pipe.forked)
     (void)pipe_join(const_cast<gar_hip_solver *>(s));
 }
 // ... and the half streams behind what the caller's stream holds (uploads, a previous unpipelined sweep)
@@ -49,22 +49,22 @@ void pipe_autojoin(const gar_hip_solver *s) {
 // stream since the first fork, a producer kernel or a copy into the records, is then waited for as gar_hip.h
 // promises; an event on a stream that holds nothing new is complete at once, so the halves keep overlapping)
 int pipe_fork(gar_hip_solver *s, bool again = false) {
-  if (s->pipe_forked && !again)
+  if (s->pipe.forked && !again)
     return GAR_HIP_OK;
-  HIP_TRY(hipEventRecord(s->pipe_evFork, s->stream));
+  HIP_TRY(hipEventRecord(s->pipe.evFork, s->stream));
   for (int h = 0; h < 2; ++h)
-    HIP_TRY(hipStreamWaitEvent(s->pipe_stream[h], s->pipe_evFork, 0));
-  s->pipe_forked = true;
+    HIP_TRY(hipStreamWaitEvent(s->pipe.stream[h], s->pipe.evFork, 0));
+  s->pipe.forked = true;
   return GAR_HIP_OK;
 }
 int pipe_backward(gar_hip_solver *s, double mueq) {
   RoctxRange range_("gar::backwardImpl+factor_initial (pipelined)");
   s->eager_fwd = false;
-  if (s->ev_pref) {
-    HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_pref, 0));
+  if (s->lazy.ev_pref) {
+    HIP_TRY(hipStreamWaitEvent(s->stream, s->lazy.ev_pref, 0));
     s->pref_b = -1;
   }
-  if (s->dirty) { // staged host data goes out on the caller's stream: order it, then fork again
+  if (s->buf.dirty) { // staged host data goes out on the caller's stream: order it, then fork again
     if (int rc = pipe_join(s))
       return rc;
     if (int rc = commit(s))
@@ -77,11 +77,11 @@ int pipe_backward(gar_hip_solver *s, double mueq) {
   for (int h = 0; h < 2; ++h) {
     int b0, nb;
     pipe_range(s, h, &b0, &nb);
-    hipStream_t st = s->pipe_stream[h];
+    hipStream_t st = s->pipe.stream[h];
     // backward sweeps alternate between the halves: this one starts when the other half's last one has ended --
     // which is also when that half's forward sweep starts (its stream's next kernel)
-    if (s->pipe_evB_valid[1 - h])
-      HIP_TRY(hipStreamWaitEvent(st, s->pipe_evB[1 - h], 0));
+    if (s->pipe.evB_valid[1 - h])
+      HIP_TRY(hipStreamWaitEvent(st, s->pipe.evB[1 - h], 0));
     HIP_TRY(hipMemsetAsync(status_words(s, b0), 0, sizeof(int) * (size_t)nb, st));
     if (h == 0) // the slow-path counters of "the last backward" cover both halves (the second half runs behind this one)
       HIP_TRY(hipMemsetAsync(status_counters(s), 0, sizeof(int) * kStatusCounters, st));
@@ -90,15 +90,15 @@ int pipe_backward(gar_hip_solver *s, double mueq) {
     M.fac += (long long)b0 * M.fac_stride;
     M.status += b0;
     M.resume += b0;
-    M.init = s->d_init + (long long)b0 * M.init_stride;
+    M.init = s->buf.d_init + (long long)b0 * M.init_stride;
     M.init_small = 1;
     M.trace = nullptr;
     if (s->timing)
-      HIP_TRY(hipEventRecord(s->pipe_evT[h][0], st));
+      HIP_TRY(hipEventRecord(s->pipe.evT[h][0], st));
     hipLaunchKernelGGL(s->wave_half_kernel, dim3((unsigned)nb), dim3(64), (size_t)s->wave_lds_doubles_small * sizeof(double),
                        st, M, nb);
     if (s->timing)
-      HIP_TRY(hipEventRecord(s->pipe_evT[h][1], st));
+      HIP_TRY(hipEventRecord(s->pipe.evT[h][1], st));
     // the problems whose initial condition is not "x0 given" (no closed form): every other wave leaves at once
     gar::GenericParams G = G0;
     G.prob += (long long)b0 * G.prob_stride;
@@ -109,8 +109,8 @@ int pipe_backward(gar_hip_solver *s, double mueq) {
     hipLaunchKernelGGL(gar::gar_initial_wave, dim3((unsigned)nb), dim3(64),
                        (size_t)gar::gar_initial_wave_lds_doubles(s->n0, s->nth0) * sizeof(double), st, G);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(s->pipe_evB[h], st));
-    s->pipe_evB_valid[h] = true;
+    HIP_TRY(hipEventRecord(s->pipe.evB[h], st));
+    s->pipe.evB_valid[h] = true;
   }
   return GAR_HIP_OK;
 }
@@ -122,17 +122,17 @@ int pipe_forward(gar_hip_solver *s) {
   for (int h = 0; h < 2; ++h) {
     int b0, nb;
     pipe_range(s, h, &b0, &nb);
-    hipStream_t st = s->pipe_stream[h];
+    hipStream_t st = s->pipe.stream[h];
     gar::MfmaFwdParams F = F0;
     F.fac += (long long)b0 * F.fac_stride;
     F.init += (long long)b0 * F.init_stride;
     F.sol += (long long)b0 * F.sol_stride;
     if (s->timing)
-      HIP_TRY(hipEventRecord(s->pipe_evT[h][2], st));
+      HIP_TRY(hipEventRecord(s->pipe.evT[h][2], st));
     hipLaunchKernelGGL(s->lean_fwd_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), s->lean_fwd_lds_bytes, st, F, nb);
     HIP_TRY(hipGetLastError());
     if (s->timing)
-      HIP_TRY(hipEventRecord(s->pipe_evT[h][3], st));
+      HIP_TRY(hipEventRecord(s->pipe.evT[h][3], st));
   }
   return GAR_HIP_OK;
 }

@@ -242,10 +242,12 @@ inline hipError_t hipMemset2DAsync(void *d, size_t pitch, int v, size_t w, size_
   for (size_t r = 0; r < h; ++r) std::memset((char *)d + r * pitch, v, w);
   return 0;
 }
-inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = nullptr; return 0; }
-inline hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int) { *s = nullptr; return 0; }
+// (a stream is a one-byte token, like an event: "created" reads as non-null, and a leaked or twice-destroyed one shows
+// under a host sanitizer; nothing dereferences it)
+inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = (hipStream_t)std::malloc(1); return 0; }
+inline hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned f, int) { return hipStreamCreateWithFlags(s, f); }
 inline hipError_t hipDeviceGetStreamPriorityRange(int *lo, int *hi) { *lo = 0; *hi = -1; return 0; }
-inline hipError_t hipStreamDestroy(hipStream_t) { return 0; }
+inline hipError_t hipStreamDestroy(hipStream_t s) { std::free(s); return 0; }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
 inline hipError_t hipGetLastError() { return 0; }
 typedef struct emu_event_t *hipEvent_t;
