@@ -63,6 +63,11 @@ SIGNATURES = {
     "gar_hip_forward": (C.c_int, [C.c_void_p, _PD]),
     "gar_hip_forward_async": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gar_hip_num_failed": (C.c_int, [C.c_void_p]),
+    "gar_hip_get_status": (C.c_int, [C.c_void_p, _PI32]),
+    "gar_hip_kkt_error_async": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "gar_hip_kkt_error": (C.c_int, [C.c_void_p, C.c_double, _PD, _PD, _PD]),
+    "gar_hip_device_kkt_errors": (C.c_void_p, [C.c_void_p]),
+    "gar_hip_device_kkt_stage_errors": (C.c_void_p, [C.c_void_p]),
     "gar_hip_slow_path_stages": (C.c_int, [C.c_void_p, _PI64]),
     "gar_hip_constrained_bk_stages": (C.c_int, [C.c_void_p, _PI64]),
     "gar_hip_boundary_doubles": (C.c_int64, [C.c_void_p]),

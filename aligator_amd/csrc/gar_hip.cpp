@@ -36,6 +36,7 @@
 #include "gar_fold.hpp"
 #include "gar_cstr_seg_api.hpp"
 #include "gar_leg_seg.hpp"
+#include "gar_kkt.hpp"
 #include "gar_host.hpp"
 
 namespace gar { // instantiated in gar_wave_sweep.cpp (its own translation unit, its own code-generation flags)
@@ -753,12 +754,12 @@ inline bool records_t2(const gar_hip_solver *s, int b) {
   return s->fb_t2 && !(s->fold && s->buf.coupled_known && s->buf.h_coupled[(size_t)b] != 0);
 }
 
-#include "gar_launch.hpp"
-
 // a kernel's opt-in to `doubles` of dynamic LDS (> 64 KiB needs it)
 template <class K> hipError_t max_lds(K kernel, size_t doubles) {
   return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(doubles * sizeof(double)));
 }
+
+#include "gar_launch.hpp"
 
 int allocate(gar_hip_solver *s) {
   const size_t B = (size_t)s->batch;
@@ -1747,6 +1748,70 @@ int gar_hip_forward(gar_hip_solver *s, const double *theta) {
   }
   if (int rc = launch_forward(s, th))
     return rc;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return GAR_HIP_OK;
+}
+
+// ---- lqrComputeKktError for the whole batch, on the device (gar_kkt.hpp; launch_kkt in gar_launch.hpp) -------------
+namespace {
+int kkt_check(const gar_hip_solver *s, const void *theta) {
+  if (!s)
+    return fail(GAR_HIP_ERR_ARG, "null solver");
+  if (s->multi)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, "device-side KKT residuals on a multi-device solver: the records live on several devices");
+  if (theta && (s->num_legs > 1 || s->nth0 == 0))
+    return fail(GAR_HIP_ERR_ARG, "gar_hip_kkt_error: theta on a solver without parameter (leg mode, or nth = 0)");
+  if (theta) // Gx theta, Gu theta of EVERY stage: a record with another column count has no product with this theta
+    for (const gar_stage_meta &m : s->meta)
+      if (((m.flags & GAR_KNOT_HAS_PARAM) ? m.nth : 0) != s->nth0)
+        return fail(GAR_HIP_ERR_ARG, "gar_hip_kkt_error: theta on a problem whose stages differ in nth");
+  return GAR_HIP_OK;
+}
+} // namespace
+
+int gar_hip_kkt_error_async(gar_hip_solver *s, double mueq, const double *theta_device) {
+  GAR_GUARD(s); // (a pipelined sweep: the solver's stream is ordered behind the half streams first)
+  if (int rc = kkt_check(s, theta_device))
+    return rc;
+  return launch_kkt(s, mueq, theta_device);
+}
+
+int gar_hip_kkt_error(gar_hip_solver *s, double mueq, const double *theta_host, double *out3, double *stage4) {
+  GAR_GUARD(s);
+  if (int rc = kkt_check(s, theta_host))
+    return rc;
+  const double *th = nullptr;
+  if (theta_host) { // staged as gar_hip_forward stages it
+    HIP_TRY(hipMemcpyAsync(s->buf.d_theta, theta_host, sizeof(double) * (size_t)s->nth0 * s->batch, hipMemcpyHostToDevice,
+                           s->stream));
+    th = s->buf.d_theta;
+  }
+  if (int rc = launch_kkt(s, mueq, th))
+    return rc;
+  int rc = d2h(s, out3, s->buf.d_kkt_err, (int64_t)s->batch * 3);
+  rc |= d2h(s, stage4, s->buf.d_kkt_stage, (int64_t)s->batch * (s->horizon + 1) * 4);
+  if (rc)
+    return rc;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return GAR_HIP_OK;
+}
+
+const double *gar_hip_device_kkt_errors(gar_hip_solver *s) {
+  pipe_autojoin(s);
+  return s && !s->multi ? s->buf.d_kkt_err.get() : nullptr;
+}
+const double *gar_hip_device_kkt_stage_errors(gar_hip_solver *s) {
+  pipe_autojoin(s);
+  return s && !s->multi ? s->buf.d_kkt_stage.get() : nullptr;
+}
+
+int gar_hip_get_status(gar_hip_solver *s, int32_t *out) {
+  GAR_GUARD(s);
+  if (!s || !out)
+    return fail(GAR_HIP_ERR_ARG, "gar_hip_get_status: bad argument");
+  GAR_MULTI(s, multi_get_status(s, out));
+  static_assert(sizeof(int) == sizeof(int32_t), "the status words are 32-bit");
+  HIP_TRY(hipMemcpyAsync(out, status_words(s), sizeof(int32_t) * (size_t)s->batch, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return GAR_HIP_OK;
 }

@@ -244,6 +244,10 @@ struct LayoutState {
   DevBuf<long long> d_gain_off;
   DevBuf<double> d_gains;
   PinnedBuf<double> h_results;
+  // gar_hip_kkt_error (gar_kkt.hpp): the stage norms [batch][horizon + 1][4] and the triples [batch][3], both on
+  // the first call or neither; the LDS one workgroup of gar_kkt_stage_residuals asks for (bytes)
+  DevBuf<double> d_kkt_stage, d_kkt_err;
+  size_t kkt_lds_bytes = 0;
 };
 
 // Solver lifetime: the pipelined sweep's half streams and events (gar_hip_set_pipeline; the serial one-wave family,

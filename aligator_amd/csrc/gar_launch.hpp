@@ -553,3 +553,61 @@ int d2h(gar_hip_solver *s, double *dst, const double *src, int64_t n) {
   HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s->stream));
   return GAR_HIP_OK;
 }
+
+// ---- the KKT residuals of the whole batch (gar_kkt.hpp): one launch sequence for every solver family ------------------
+gar::KktParams make_kkt_params(gar_hip_solver *s, double mueq, const double *theta_dev) {
+  gar::KktParams K{};
+  K.meta = s->buf.d_meta; // the caller-facing records, also on a folded solver (d_meta2 / d_prob2 stay inside the library)
+  K.prob = s->buf.d_prob;
+  K.sol = s->buf.d_sol;
+  K.theta = theta_dev;
+  K.stage = s->buf.d_kkt_stage;
+  K.err = s->buf.d_kkt_err;
+  K.prob_stride = s->prob_doubles;
+  K.sol_stride = s->sol_doubles;
+  K.G0_off = s->G0_off;
+  K.g0_off = s->g0_off;
+  K.horizon = s->horizon;
+  K.nc0 = s->nc0;
+  K.nth0 = s->nth0;
+  K.qr_packed = s->qr_packed ? 1 : 0;
+  K.mueq = mueq;
+  return K;
+}
+
+// the two result buffers, on the first call after the layout was built (both or neither), and the kernel's LDS
+int kkt_buffers(gar_hip_solver *s) {
+  if (s->buf.d_kkt_stage)
+    return GAR_HIP_OK;
+  if ((int64_t)s->batch * (s->horizon + 1) > INT32_MAX) // one workgroup per (problem, stage), all of them in grid.x
+    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_kkt_error: batch x (horizon + 1) above 2^31 - 1 workgroups");
+  int lds = 0; // (the knot is tiled, the stage's vectors are not: they bound the dimensions, below)
+  for (const gar_stage_meta &m : s->meta)
+    lds = std::max(lds, gar::kkt_lds_doubles(m.nx, m.nu, m.nc, m.nx2, m.nth, s->nc0));
+  const size_t bytes = (size_t)lds * sizeof(double);
+  if (bytes > kCuLdsBytes)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_kkt_error: the stage vectors need " + std::to_string(bytes) +
+                                             " B of LDS (> 160 KiB per CU)");
+  HIP_TRY(max_lds(gar::gar_kkt_stage_residuals, (size_t)lds));
+  DevBuf<double> st, er;
+  HIP_TRY(st.zalloc((size_t)s->batch * (size_t)(s->horizon + 1) * 4));
+  HIP_TRY(er.zalloc((size_t)s->batch * 3));
+  s->buf.d_kkt_stage = std::move(st);
+  s->buf.d_kkt_err = std::move(er);
+  s->buf.kkt_lds_bytes = bytes;
+  return GAR_HIP_OK;
+}
+
+int launch_kkt(gar_hip_solver *s, double mueq, const double *theta_dev) {
+  RoctxRange range_("gar::lqrComputeKktError");
+  if (int rc = kkt_buffers(s))
+    return rc;
+  if (int rc = commit(s)) // knots the host staged since the last sweep
+    return rc;
+  const gar::KktParams K = make_kkt_params(s, mueq, theta_dev);
+  hipLaunchKernelGGL(gar::gar_kkt_stage_residuals, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)),
+                     dim3(GAR_KKT_THREADS), s->buf.kkt_lds_bytes, s->stream, K);
+  hipLaunchKernelGGL(gar::gar_kkt_reduce, dim3((unsigned)s->batch), dim3(64), 0, s->stream, K);
+  HIP_TRY(hipGetLastError());
+  return GAR_HIP_OK;
+}

@@ -273,6 +273,20 @@ int multi_num_failed(gar_hip_solver *s) {
   return n;
 }
 
+// the status words of every device, OR-ed per problem (gar_hip_get_status)
+int multi_get_status(gar_hip_solver *s, int32_t *out) {
+  std::vector<int> st((size_t)s->batch);
+  std::fill(out, out + s->batch, 0);
+  for (gar_hip_solver *q : s->multi->subs) {
+    DeviceGuard g(q->device);
+    HIP_TRY(hipMemcpyAsync(st.data(), q->buf.d_status, sizeof(int) * st.size(), hipMemcpyDeviceToHost, q->stream));
+    HIP_TRY(hipStreamSynchronize(q->stream));
+    for (size_t i = 0; i < st.size(); ++i)
+      out[i] |= st[i];
+  }
+  return GAR_HIP_OK;
+}
+
 int multi_counters(gar_hip_solver *s, int64_t out[2], int (*get)(gar_hip_solver *, int64_t *)) {
   if (!out)
     return fail(GAR_HIP_ERR_ARG, "bad argument");

@@ -440,6 +440,41 @@ class BatchedRiccatiSolver:
     def num_failed(self) -> int:
         return self._L.gar_hip_num_failed(self._h)
 
+    def status(self) -> np.ndarray:
+        """gar_hip_get_status: the per-problem status words of the last backward, int32 (batch,); 0 = success
+        (include/gar_hip.h lists the bits)."""
+        out = np.zeros(self.batch, dtype=np.int32)
+        self._check(self._L.gar_hip_get_status(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def kkt_error(self, mueq: float, theta: Optional[np.ndarray] = None, stages: bool = False):
+        """lqrComputeKktError (gar/utils.hxx:88-182) of every problem of the batch, formed on the device from the
+        resident knots and the last forward's solution (gar_hip_kkt_error): -> (batch, 3) = dynErr, cstErr, dualErr;
+        with stages=True also (batch, horizon + 1, 4) = the per-stage infinity norms dyn, cst, gx, gu.
+        theta: nth * batch doubles, batch-major (serial solvers with nth > 0 only)."""
+        th = None
+        if theta is not None:
+            theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(-1)
+            nth0 = self.effective_nth(0) if self.num_legs == 1 else 0
+            if nth0 > 0 and theta.size != nth0 * self.batch:
+                raise ValueError(f"theta has {theta.size} entries, expected nth * batch = {nth0 * self.batch}")
+            th = theta.ctypes.data_as(_PD)
+        out = np.zeros((self.batch, 3))
+        st = np.zeros((self.batch, self.horizon + 1, 4)) if stages else None
+        self._check(self._L.gar_hip_kkt_error(self._h, float(mueq), th, _ptr(out), _ptr(st)))
+        return (out, st) if stages else out
+
+    def kkt_error_async(self, mueq: float, theta_device_ptr: int = 0):
+        """gar_hip_kkt_error_async: enqueued behind the last forward_async, not waited for; read the results through
+        device_kkt_errors() (or a later kkt_error)."""
+        self._check(self._L.gar_hip_kkt_error_async(self._h, float(mueq), C.c_void_p(theta_device_ptr)))
+
+    def device_kkt_errors(self):
+        """(triples [batch][3], stage norms [batch][horizon + 1][4]) device addresses; None before the first
+        kkt_error / kkt_error_async."""
+        L, h = self._L, self._h
+        return L.gar_hip_device_kkt_errors(h), L.gar_hip_device_kkt_stage_errors(h)
+
     def slow_path_stages(self):
         """(stages of the last backward that left the register LDL^T because Rhat failed the first
         Bunch-Kaufman test, those of them where Bunch-Kaufman really pivoted), summed over the batch."""

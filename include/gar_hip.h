@@ -297,6 +297,48 @@ int gar_hip_backward_blocks(gar_hip_solver *s, const double *const *blocks, cons
 /* number of problems whose backward reported a failed factorisation */
 int gar_hip_num_failed(gar_hip_solver *s);
 
+/* The per-problem status words of the last backward, out[batch]: 0 = every factorisation of the problem succeeded.
+ * The kernels OR bits into a problem's word: 1 = a stage's reduced KKT matrix hit an exactly-zero pivot column
+ * (the reference's "failed stage" exception, riccati-kernel.hxx:239-241), 2 = the initial stage's kkt0 did
+ * (proximal-riccati.hxx:48-50), 4 = a block of the condensed system did (leg mode).  gar_hip_num_failed counts the
+ * non-zero words.  Synchronous.  A multi-device handle: the words of its devices, OR-ed. */
+int gar_hip_get_status(gar_hip_solver *s, int32_t *out /* batch */);
+
+/* ---- KKT residuals of the whole batch, on the device (lqrComputeKktError, gar/utils.hxx:88-182) ---------------------
+ * The quantity every test of the reference asserts on, for all `batch` problems at once and without the problems or
+ * the solutions leaving HBM (csrc/gar_kkt.hpp).  Reads what is there: the knot records as gar_hip_device_problems
+ * describes them (uploaded, or written in place by gar_hip_update_lq_subproblem_device / a device producer; host
+ * uploads still staged are flushed first) and the solution records the last gar_hip_forward left -- it does not sweep.
+ * Per problem: dynErr = max_t |A x + B u + f - x'| (and |g0 + G0 x0|), cstErr = max_t |C x + D u + d - mueq v|,
+ * dualErr = max_t max(|gx|, |gu|), infinity norms, term by term the reference's (utils.hxx:116-178; its _gt is not
+ * part of the triple and is not formed).  One difference, stated: a non-finite residual entry makes its norm
+ * non-finite (NaN or inf) -- std::max in the reference drops a NaN in second position; numpy's max, which the Python
+ * mirror uses, does not.
+ *   gar_hip_kkt_error_async   enqueued on the solver's stream behind the last forward, in whichever schedule the solver
+ *                             runs (pipelined: the half streams are joined first, as by the getters); theta_device:
+ *                             ntheta doubles per problem, batch-major, on the device, or NULL.  Not waited for.
+ *   gar_hip_kkt_error         the same, synchronous: theta_host is staged as gar_hip_forward stages it, then
+ *                             out3 [batch][3] = dynErr, cstErr, dualErr and stage4 [batch][horizon + 1][4] = the
+ *                             per-stage norms dyn, cst, gx, gu (stage 0's dyn slot carries the initial condition, the
+ *                             terminal stage's is 0) are copied back; either may be NULL.
+ *   gar_hip_device_kkt_errors / gar_hip_device_kkt_stage_errors   the two result buffers on the device, for consumers
+ *                             that stay there; NULL before the first call (they are allocated by it, not by create:
+ *                             gar_hip_debug_alloc_count rises by two on the first call and not again) and after a
+ *                             gar_hip_cycle_append that rebuilt the layout.
+ * theta is accepted only on a serial solver whose knots carry a parameter (nth > 0); non-NULL in leg mode or with
+ * nth = 0, or on a problem whose stages differ in nth: GAR_HIP_ERR_ARG.  Limits (GAR_HIP_ERR_UNSUPPORTED): batch x
+ * (horizon + 1) at most 2^31 - 1 (one workgroup each, in grid.x: a batch above 65 535 is served as by the sweeps); the
+ * knot is tiled through LDS whatever its size, the stage's twelve vectors are not and must fit a CU's LDS beside the
+ * tile (about 2 nx + 2 nu + 2 nc + max(nx, nc0) + 3 nx2 + nth + nc0 <= 16 384).  Every single-device solver is served, whatever kernel family sweeps it -- padded ones
+ * too: the dummy states and controls solve to exactly zero and add nothing to any norm.  On a multi-device handle
+ * (gar_hip_multi_create) the records live on several devices: GAR_HIP_ERR_UNSUPPORTED / NULL, like the other entry
+ * points that take or return device pointers. */
+int gar_hip_kkt_error_async(gar_hip_solver *s, double mueq, const double *theta_device);
+int gar_hip_kkt_error(gar_hip_solver *s, double mueq, const double *theta_host, double *out3 /* batch x 3, may be NULL */,
+                      double *stage4 /* batch x (N+1) x 4, may be NULL */);
+const double *gar_hip_device_kkt_errors(gar_hip_solver *s);       /* [batch][3]      */
+const double *gar_hip_device_kkt_stage_errors(gar_hip_solver *s); /* [batch][N+1][4] */
+
 /* Diagnostics of the last backward (specialised kernel families; no reference counterpart): the
  * register LDL^T of Rhat is what Bunch-Kaufman does whenever its first test |a_kk| >= alpha*colmax
  * holds at every column (bunchkaufman.hpp:61); out[0] = stages (summed over the batch) where it did
