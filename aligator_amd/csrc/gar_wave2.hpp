@@ -367,6 +367,40 @@ __device__ __forceinline__ int wave_ldl_fast_neg_pre(int lane, double (&a)[NU], 
   return bad;
 }
 
+// wave_ldl_fast_neg_pre under spd_accept with ONE verdict per factorisation (the plain stage, NU <= 16).  Under
+// spd_accept the per-column routine never looks further at a column that fails the first test: all it keeps is whether
+// any did, and whether every pivot was positive.  So the column loop here only accumulates the lanes that fail and the
+// sign of the pivots -- no branch, no call, nothing of the second test's code in the way -- and the verdict is formed
+// behind the last column.  The elimination is the per-column routine's, operation for operation: L, -1/d,
+// `first_failed` and the return value are the same in every case (no lane failed: 0; some lane failed: 0 iff every
+// pivot was positive).  The literal rule (GAR_HIP_SPD_ACCEPT=0) stays on the per-column routine.
+template <int NU>
+__device__ __forceinline__ int wave_ldl_fast_neg_spd(int lane, double (&a)[NU], double (&nd)[NU], bool &first_failed) {
+  static_assert(NU <= 16, "the rows sit in one DPP row");
+  const double alpha = (1.0 + 4.123105625617661) / 8.0;
+  unsigned long long failing = 0ull;
+  double minpiv = 1.0; // smallest pivot so far (wave-uniform); NaN-safe: the comparison below is !(x > 0)
+#pragma unroll
+  for (int k = 0; k < NU; ++k) {
+    const double akk = ldl_bcast<NU>(a[k], k, lane);
+    minpiv = !(akk > 0.0) ? -1.0 : minpiv;
+    // (one ballot per comparison: each is the v_cmp's own result; the ballot of their `||` goes through a select)
+    const unsigned long long nok = wave_ballot(!(fabs(akk) >= alpha * fabs(a[k]))) | wave_ballot(akk == 0.0);
+    failing |= nok & (((1ull << NU) - 1ull) & ~((1ull << k) - 1ull));
+    const double nd_k = -fast_rcp(akk);
+    const double nlik = a[k] * nd_k; // -L(i,k)
+#pragma unroll
+    for (int j = k + 1; j < NU; ++j)
+      a[j] = __builtin_fma(ldl_bcast<NU>(nlik, j, lane), a[k], a[j]); // a(i,j) -= L(j,k) a(i,k)
+    a[k] = nlik;
+    nd[k] = nd_k;
+  }
+  first_failed = failing != 0ull;
+  if (!first_failed)
+    return 0;
+  return __builtin_amdgcn_readfirstlane(minpiv > 0.0 ? 0 : 1);
+}
+
 // A memory instruction issued right behind a v_mfma_f64_16x16x4 costs ~8 cycles of the wave's time
 // instead of ~20 (the MFMA holds the VALU for 64 cycles; LDS and memory instructions of the same
 // wave keep issuing: scripts/ubench/overlap.cpp).  The compiler's scheduler clusters memory
@@ -703,7 +737,14 @@ __device__ __forceinline__ int wave_stage2(const MfmaParams &P, double *sm, cons
     verdict = wave_ldl_fast_neg_pre<NK, 1>(lane, a44, nd44, first_failed, nd44p);
 #endif
   } else {
-    verdict = wave_ldl_fast_neg_pre<NU>(lane, a_row, nd, first_failed, nullptr, P.spd_accept != 0);
+    if constexpr (NC == 0 && NU <= 16) { // the plain stage: in its default mode one verdict per factorisation
+      if (P.spd_accept != 0)
+        verdict = wave_ldl_fast_neg_spd<NU>(lane, a_row, nd, first_failed);
+      else
+        verdict = wave_ldl_fast_neg_pre<NU>(lane, a_row, nd, first_failed, nullptr, false);
+    } else {
+      verdict = wave_ldl_fast_neg_pre<NU>(lane, a_row, nd, first_failed, nullptr, P.spd_accept != 0);
+    }
   }
   if (first_failed && lane == 0) { // diagnostics: stages that needed the second test / that really pivot
     atomicAdd(&P.slow[0], 1);
