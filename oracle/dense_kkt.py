@@ -21,7 +21,7 @@ def lqr_dense_matrix(problem, mueq: float):
     for t, k in enumerate(knots):
         nrows += k.nx + k.nu + k.nc
         if t != N:
-            nrows += k.nx
+            nrows += k.nx2          # (lbd_{t+1} has nx2 rows: not nx where the state dimension varies)
     mat = np.zeros((nrows, nrows))
     rhs = np.zeros(nrows)
     nx0 = knots[0].nx
