@@ -1,9 +1,11 @@
-// gar_entry_io.hpp -- the caller-facing entry points whose records differ from the device's under padding (gar_hip_solver::padded) or for a normalised terminal knot -- upload_stage, set_init, packed up / download, the getters -- the device-layout getters and the debug counters (inside extern "C").
+// gar_entry_io.hpp -- the caller-facing entry points that convert between the caller's blocks and the device's records:
+// gar_hip_upload_stage, gar_hip_set_init and the per-stage getters (gains, value function, kktMat, initial stage,
+// solution), each ONE body for padded and unpadded solvers over the block maps of gar_record_io.hpp; behind them the
+// condensed-solve queries, the device-layout getters and the debug counters (inside extern "C").
 // Part of the ONE translation unit gar_hip.cpp (included in place: it uses the solver struct and the helpers defined
 // above its include line); split out for readability only.
 #pragma once
 
-// ---- caller-facing entry points whose records differ under padding (gar_hip_solver::padded) --------------------
 int gar_hip_upload_stage(gar_hip_solver *s, int b, int t, const double *Q, const double *S, const double *R,
                          const double *q, const double *r, const double *A, const double *B, const double *f,
                          const double *C, const double *D, const double *d, const double *Gth, const double *Gx,
@@ -12,65 +14,16 @@ int gar_hip_upload_stage(gar_hip_solver *s, int b, int t, const double *Q, const
   if (int rc = check_bt(s, b, t))
     return rc;
   GAR_MULTI(s, gar_hip_upload_stage(multi_owner(s, t), b, t, Q, S, R, q, r, A, B, f, C, D, d, Gth, Gx, Gu, Gv, gamma));
-  return upload_stage_impl(s, b, t, Q, S, R, q, r, A, B, f, C, D, d, Gth, Gx, Gu, Gv, gamma);
-}
-
-static int upload_stage_impl(gar_hip_solver *s, int b, int t, const double *Q, const double *S, const double *R,
-                             const double *q, const double *r, const double *A, const double *B, const double *f,
-                             const double *C, const double *D, const double *d, const double *Gth, const double *Gx,
-                             const double *Gu, const double *Gv, const double *gamma) {
   if (s->term_grown && t == s->horizon) // the caller's terminal A (0 x nx) and f are empty: zeros in the record
     A = f = s->term_zeros.data();
-  if (!s->padded)
-    return upload_stage_dev(s, b, t, Q, S, R, q, r, A, B, f, C, D, d, Gth, Gx, Gu, Gv, gamma);
-  const gar_stage_meta &m = s->meta[t];
-  const int nx = s->unx, nu = m.nu > 0 ? s->unu : 0, NX = m.nx, NU = m.nu;
-  if (!Q || !q || !A || !f || (nu > 0 && (!S || !R || !r || !B)))
+  const gar_stage_meta &u = caller_layout(s).meta[t], &m = s->meta[t];
+  if (!Q || !q || !A || !f || (u.nu > 0 && (!S || !R || !r || !B)))
     return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_stage: null block");
-  if (s->buf.staged) {
-    // straight into the pinned staging record, one pass: real rows / columns copied column by column, the dummy
-    // ones written beside them (no intermediate padded copy of the blocks); then the knot is one dirty range
-    const gar_knot_offsets o = gar_knot_layout(NX, NU, 0, NX, 0);
-    double *rec = s->buf.h_prob + (int64_t)b * s->prob_doubles + m.in_off;
-    const bool nt = s->buf.stage_nt;
-    auto put = [rec, nt](int64_t off, const double *src, int r, int c, int R, int C, double diag) {
-      double *dst = rec + off;
-      if (r == R) { // same column pitch (e.g. (56, 22) -> (56, 24): only controls are added): the real columns in one go
-        stage_copy(dst, src, (size_t)r * (size_t)c, nt);
-      } else {
-        for (int j = 0; j < c; ++j) {
-          std::memcpy(dst + (size_t)j * R, src + (size_t)j * r, sizeof(double) * (size_t)r);
-          std::memset(dst + (size_t)j * R + r, 0, sizeof(double) * (size_t)(R - r));
-        }
-      }
-      if (C > c)
-        std::memset(dst + (size_t)c * R, 0, sizeof(double) * (size_t)R * (size_t)(C - c));
-      if (diag != 0.0)
-        for (int i = std::min(r, c); i < std::min(R, C); ++i)
-          dst[(size_t)i * R + i] = diag;
-    };
-    if (s->qr_packed && t < s->horizon) {
-      pack_lower(rec + o.Q, Q, nx, NX, 1.0);
-      pack_lower(rec + o.R, R, nu, NU, 1.0);
-    } else {
-      put(o.Q, Q, nx, nx, NX, NX, 1.0);
-      put(o.R, R, nu, nu, NU, NU, 1.0);
-    }
-    put(o.S, S, nx, nu, NX, NU, 0.0);
-    put(o.q, q, nx, 1, NX, 1, 0.0);
-    put(o.r, r, nu, 1, NU, 1, 0.0);
-    put(o.A, A, nx, nx, NX, NX, 0.0);
-    put(o.B, B, nx, nu, NX, NU, 0.0);
-    put(o.f, f, nx, 1, NX, 1, 0.0);
-    mark_dirty(s, b, m.in_off, m.in_off + gar_knot_doubles(NX, NU, 0, NX, 0));
-    return flush_if_grown(s, b);
-  }
-  thread_local std::vector<double> bQ, bS, bR, bq, br, bA, bB, bf;
-  return upload_stage_dev(s, b, t, padded_block(bQ, Q, nx, nx, NX, NX, 1.0), padded_block(bS, S, nx, nu, NX, NU, 0.0),
-                          padded_block(bR, R, nu, nu, NU, NU, 1.0), padded_block(bq, q, nx, 1, NX, 1, 0.0),
-                          padded_block(br, r, nu, 1, NU, 1, 0.0), padded_block(bA, A, nx, nx, NX, NX, 0.0),
-                          padded_block(bB, B, nx, nu, NX, NU, 0.0), padded_block(bf, f, nx, 1, NX, 1, 0.0), nullptr,
-                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  const int nth_st = (m.flags & GAR_KNOT_HAS_PARAM) ? m.nth : 0;
+  BlockMap maps[16];
+  knot_block_maps(maps, u, m, nth_st, s->qr_packed && t < s->horizon);
+  const double *const src[16] = {Q, S, R, q, r, A, B, f, C, D, d, Gth, Gx, Gu, Gv, gamma};
+  return write_blocks(s, b, m.in_off, gar_knot_doubles(m.nx, m.nu, m.nc, m.nx2, nth_st), maps, src, 16);
 }
 
 int gar_hip_set_init(gar_hip_solver *s, int b, const double *G0, const double *g0) {
@@ -78,23 +31,13 @@ int gar_hip_set_init(gar_hip_solver *s, int b, const double *G0, const double *g
   if (int rc = check_bt(s, b, 0))
     return rc;
   GAR_MULTI(s, multi_set_init(s, b, G0, g0));
-  if (!s->padded)
-    return set_init_dev(s, b, G0, g0);
   if (s->user_nc0 > 0 && (!G0 || !g0))
     return fail(GAR_HIP_ERR_ARG, "gar_hip_set_init: null block");
-  // [G0 0; 0 -I], [g0; 0]: the dummy states start (and stay) at zero
-  const int nc0u = s->user_nc0, nc0 = s->nc0, nx = s->unx, NX = s->pnx;
-  thread_local std::vector<double> G, g;
-  G.assign((size_t)nc0 * NX, 0.0);
-  g.assign((size_t)nc0, 0.0);
-  for (int j = 0; j < nx; ++j)
-    for (int i = 0; i < nc0u; ++i)
-      G[(size_t)j * nc0 + i] = G0[(size_t)j * nc0u + i];
-  for (int i = 0; i < NX - nx; ++i)
-    G[(size_t)(nx + i) * nc0 + nc0u + i] = -1.0;
-  for (int i = 0; i < nc0u; ++i)
-    g[i] = g0[i];
-  return set_init_dev(s, b, G.data(), g.data());
+  const gar::HostLayout &u = caller_layout(s);
+  BlockMap maps[2];
+  init_block_maps(maps, u.nc0, u.nx0, s->nc0, s->nx0, s->G0_off, s->g0_off, u.G0_off, u.g0_off);
+  const double *const src[2] = {G0, g0};
+  return write_blocks(s, b, 0, s->g0_off + s->nc0, maps, src, 2);
 }
 
 int gar_hip_set_condensed_backward_ok(gar_hip_solver *s, double omega) {
@@ -177,43 +120,36 @@ int gar_hip_get_gains(gar_hip_solver *s, int b, int t, double *ff, double *fb, d
   if (int rc = check_bt(s, b, t))
     return rc;
   GAR_MULTI(s, gar_hip_get_gains(multi_owner(s, t), b, t, ff, fb, fth));
-  if (s->term_grown && t == s->horizon) {
-    // the caller's terminal knot has nx2 = 0: its ff / fb / fth hold the nc rows [zff | Z | Zth] alone (they lead
-    // the record's rows; a padded solver has nc = 0: nothing to hand back)
-    const gar_stage_meta &m = s->meta[t];
-    const int nc = m.nc, NR = m.nu + m.nc + m.nx2, NX = m.nx, NT = m.nth;
-    if (nc == 0 || s->padded)
-      return GAR_HIP_OK;
-    std::vector<double> F((size_t)NR), Fb((size_t)NR * NX), Ft((size_t)NR * std::max(NT, 1));
-    if (int rc = get_gains_dev(s, b, t, F.data(), Fb.data(), NT > 0 ? Ft.data() : nullptr))
-      return rc;
-    if (ff)
-      std::copy(F.begin(), F.begin() + nc, ff);
-    if (fb)
-      std::copy(Fb.begin(), Fb.begin() + (size_t)nc * NX, fb);
-    if (fth && NT > 0)
-      std::copy(Ft.begin(), Ft.begin() + (size_t)nc * NT, fth);
-    return GAR_HIP_OK;
-  }
-  if (!s->padded)
-    return get_gains_dev(s, b, t, ff, fb, fth);
   const gar_stage_meta &m = s->meta[t];
-  const int NR = m.nu + m.nx2, NX = m.nx, NT = m.nth;
-  const int nx = s->unx, nu = m.nu > 0 ? s->unu : 0, nr = nu + nx, nt = NT > 0 ? nx : 0;
-  std::vector<double> F((size_t)NR), Fb((size_t)NR * NX), Ft((size_t)NR * std::max(NT, 1));
-  if (int rc = get_gains_dev(s, b, t, F.data(), Fb.data(), NT > 0 ? Ft.data() : nullptr))
-    return rc;
-  for (int r = 0; r < nr; ++r) {
-    const int rd = gain_row(s, r, m.nu);
-    if (ff)
-      ff[r] = F[(size_t)rd];
-    if (fb)
-      for (int j = 0; j < nx; ++j)
-        fb[(size_t)r * nx + j] = Fb[(size_t)rd * NX + j];
-    if (fth)
-      for (int j = 0; j < nt; ++j)
-        fth[(size_t)r * nt + j] = Ft[(size_t)rd * NT + j];
+  const int nx2r = s->dense ? 2 * m.nx2 : m.nx2; // stage-dense solver: rows [K; Z; L; Y]
+  const int NR = m.nu + m.nc + nx2r, NX = m.nx, NT = m.nth;
+  // the caller's rows and columns: all of them; under padding the real controls and states; of a terminal knot given
+  // with nx2 = 0 the nc rows [zff | Z | Zth] that lead the record's (a padded solver has nc = 0: nothing to hand back)
+  RowMap rows{NR, NR, 0};
+  int nx = NX, nt = NT;
+  if (s->term_grown && t == s->horizon) {
+    if (m.nc == 0 || s->padded)
+      return GAR_HIP_OK;
+    rows = RowMap{m.nc, m.nc, 0};
+  } else if (s->padded) {
+    const int nu = m.nu > 0 ? s->unu : 0;
+    rows = RowMap{nu + s->unx, nu, m.nu - nu};
+    nx = s->unx;
+    nt = NT > 0 ? nx : 0;
   }
+  if (int rc = ensure_expanded(s))
+    return rc;
+  const gar_factor_offsets o = gar_factor_layout(NX, m.nu, m.nc, nx2r, NT);
+  std::vector<double> rec((size_t)o.Vxx); // ff | fb | fth lead the factor record: one copy
+  if (int rc = d2h(s, rec.data(), s->buf.d_fac + (int64_t)b * s->fac_doubles + m.fac_off, o.Vxx))
+    return rc;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  // the specialised kernel families keep fb (and fth) in the fbT2 device order; back to StageFactor's row-major
+  // [K; Z; Aff] (riccati-kernel.hpp:96-97)
+  const bool t2 = records_t2(s, b) && t < s->horizon;
+  take_gains(ff, rec.data() + o.ff, false, NR, 1, rows, 1);
+  take_gains(fb, rec.data() + o.fb, t2, NR, NX, rows, nx);
+  take_gains(fth, rec.data() + o.fth, t2, NR, NT, rows, nt);
   return GAR_HIP_OK;
 }
 
@@ -223,28 +159,25 @@ int gar_hip_get_value(gar_hip_solver *s, int b, int t, double *Vxx, double *vx, 
   if (int rc = check_bt(s, b, t))
     return rc;
   GAR_MULTI(s, gar_hip_get_value(multi_owner(s, t), b, t, Vxx, vx, Vxt, Vtt, vt));
-  if (!s->padded)
-    return get_value_dev(s, b, t, Vxx, vx, Vxt, Vtt, vt);
-  const gar_stage_meta &m = s->meta[t];
-  const int NX = m.nx, NT = m.nth, nx = s->unx, nt = NT > 0 ? nx : 0;
-  std::vector<double> V((size_t)NX * NX), v((size_t)NX), Xt((size_t)NX * std::max(NT, 1)),
-      Tt((size_t)std::max(NT, 1) * std::max(NT, 1)), tv((size_t)std::max(NT, 1));
-  if (int rc = get_value_dev(s, b, t, V.data(), v.data(), Xt.data(), Tt.data(), tv.data()))
+  if (int rc = ensure_expanded(s))
     return rc;
-  for (int j = 0; j < nx; ++j) {
-    if (Vxx)
-      std::memcpy(Vxx + (size_t)j * nx, &V[(size_t)j * NX], sizeof(double) * (size_t)nx);
-    if (vx)
-      vx[j] = v[(size_t)j];
-  }
-  for (int j = 0; j < nt; ++j) {
-    if (Vxt)
-      std::memcpy(Vxt + (size_t)j * nx, &Xt[(size_t)j * NX], sizeof(double) * (size_t)nx);
-    if (Vtt)
-      std::memcpy(Vtt + (size_t)j * nt, &Tt[(size_t)j * NT], sizeof(double) * (size_t)nt);
-    if (vt)
-      vt[j] = tv[(size_t)j];
-  }
+  const gar_stage_meta &m = s->meta[t];
+  const gar_factor_offsets o = gar_factor_layout(m.nx, m.nu, m.nc, s->dense ? 2 * m.nx2 : m.nx2, m.nth);
+  const int NX = m.nx, NT = m.nth, nx = s->padded ? s->unx : NX, nt = s->padded ? (NT > 0 ? nx : 0) : NT;
+  std::vector<double> rec((size_t)(o.total - o.Vxx)); // Vxx | vx | Vxt | Vtt | vt close the factor record: one copy
+  if (int rc = d2h(s, rec.data(), s->buf.d_fac + (int64_t)b * s->fac_doubles + m.fac_off + o.Vxx, o.total - o.Vxx))
+    return rc;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  // (the serial one-wave family keeps the lower triangle of Vxx, packed: gar_layout.h)
+  const struct { double *dst; BlockMap map; } out[5] = {
+      {Vxx, {nx, nx, NX, NX, 0, 0, 0.0, s->vxx_packed ? kSym : kFull}},
+      {vx, {nx, 1, NX, 1, o.vx - o.Vxx, 0, 0.0, kFull}},
+      {Vxt, {nx, nt, NX, NT, o.Vxt - o.Vxx, 0, 0.0, kFull}},
+      {Vtt, {nt, nt, NT, NT, o.Vtt - o.Vxx, 0, 0.0, kFull}},
+      {vt, {nt, 1, NT, 1, o.vt - o.Vxx, 0, 0.0, kFull}}};
+  for (const auto &e : out)
+    if (e.dst)
+      take_block(e.dst, e.map, rec.data());
   return GAR_HIP_OK;
 }
 
@@ -253,19 +186,43 @@ int gar_hip_get_kkt(gar_hip_solver *s, int b, int t, double mueq, double *out) {
   if (int rc = check_bt(s, b, t))
     return rc;
   GAR_MULTI(s, gar_hip_get_kkt(multi_owner(s, t), b, t, mueq, out));
-  if (!s->padded)
-    return get_kkt_dev(s, b, t, mueq, out);
+  if (s->dense)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, "kktMat of the stage-dense solver is not kept (the whole stage matrix: gar_dense.hpp)");
   if (!out)
     return fail(GAR_HIP_ERR_ARG, "null output");
-  const gar_stage_meta &m = s->meta[t];
-  const int NU = m.nu, nu = NU > 0 ? s->unu : 0;
-  if (nu == 0)
-    return GAR_HIP_OK;
-  std::vector<double> K((size_t)NU * NU);
-  if (int rc = get_kkt_dev(s, b, t, mueq, K.data()))
+  if (int rc = ensure_expanded(s))
     return rc;
-  for (int j = 0; j < nu; ++j)
-    std::memcpy(out + (size_t)j * nu, &K[(size_t)j * NU], sizeof(double) * (size_t)nu);
+  const gar_stage_meta &m = s->meta[t];
+  const int nk = m.nu + m.nc;
+  if (nk == 0)
+    return GAR_HIP_OK;
+  if ((int64_t)nk * nk > s->buf.kkt_doubles) {
+    s->buf.kkt_doubles = 0;
+    HIP_TRY(s->buf.d_kkt.alloc((size_t)nk * nk)); // (lets the smaller one go first)
+    s->buf.kkt_doubles = (int64_t)nk * nk;
+  }
+  if (commit(s) != GAR_HIP_OK)
+    return GAR_HIP_ERR_DEVICE;
+  const int nth_st = (m.flags & GAR_KNOT_HAS_PARAM) ? m.nth : 0;
+  const gar_knot_offsets ko = gar_knot_layout(m.nx, m.nu, m.nc, m.nx2, nth_st);
+  const double *knot = s->buf.d_prob + (int64_t)b * s->prob_doubles + m.in_off;
+  // the stage's value-function term: none at the terminal knot and at the last knot of a leg (each leg ends
+  // with terminalSolve, parallel-solver.hxx:150-160)
+  const double *Vn = nullptr;
+  if (t < s->horizon && !(m.flags & GAR_KNOT_LEG_END) && m.nu > 0) {
+    const gar_stage_meta &mn = s->meta[t + 1];
+    const gar_factor_offsets fn = gar_factor_layout(mn.nx, mn.nu, mn.nc, mn.nx2, mn.nth);
+    Vn = s->buf.d_fac + (int64_t)b * s->fac_doubles + mn.fac_off + fn.Vxx;
+  }
+  hipLaunchKernelGGL(gar::gar_kkt_matrix, dim3(1), dim3(256), 0, s->stream, knot, ko, Vn, m.nx2, m.nu, m.nc, mueq,
+                     s->buf.d_kkt.get(), s->vxx_packed ? 1 : 0, (s->qr_packed && t < s->horizon) ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> K((size_t)nk * nk);
+  if (int rc = d2h(s, K.data(), s->buf.d_kkt, (int64_t)nk * nk))
+    return rc;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  const int n = s->padded ? s->unu : nk; // (a padded solver is unconstrained: the real controls' corner)
+  take_block(out, BlockMap{n, n, nk, nk, 0, 0, 0.0, kFull}, K.data());
   return GAR_HIP_OK;
 }
 
@@ -275,27 +232,21 @@ int gar_hip_get_initial(gar_hip_solver *s, int b, double *kkt0_ff, double *kkt0_
   if (int rc = check_bt(s, b, 0))
     return rc;
   GAR_MULTI(s, gar_hip_get_initial(s->multi->subs[0], b, kkt0_ff, kkt0_fth, thGrad, thHess));
-  if (!s->padded)
-    return get_initial_dev(s, b, kkt0_ff, kkt0_fth, thGrad, thHess);
-  const int n0 = s->n0, NT = s->nth0, NX = s->pnx, nx = s->unx, nt = NT > 0 ? nx : 0, n0u = nx + s->user_nc0;
-  std::vector<double> F((size_t)n0), Ft((size_t)n0 * std::max(NT, 1)), g((size_t)std::max(NT, 1)),
-      H((size_t)std::max(NT, 1) * std::max(NT, 1));
-  if (int rc = get_initial_dev(s, b, F.data(), Ft.data(), g.data(), H.data()))
+  const int n0 = s->n0, NT = s->nth0, NX = s->nx0;
+  // kkt0.ff = [x0; lbd0]: under padding the real entries of each part
+  const int nx = s->padded ? s->unx : NX, nt = s->padded ? (NT > 0 ? nx : 0) : NT;
+  const RowMap rows = s->padded ? RowMap{nx + s->user_nc0, nx, NX - nx} : RowMap{n0, n0, 0};
+  const int64_t o_fth = n0, o_g = o_fth + (int64_t)n0 * NT, o_H = o_g + NT, total = o_H + (int64_t)NT * NT;
+  std::vector<double> rec((size_t)total);
+  if (int rc = d2h(s, rec.data(), s->buf.d_init + (int64_t)b * s->init_doubles, total))
     return rc;
-  for (int r = 0; r < n0u; ++r) { // kkt0.ff = [x0; lbd0]: the real entries of each part
-    const int rd = r < nx ? r : r - nx + NX;
-    if (kkt0_ff)
-      kkt0_ff[r] = F[(size_t)rd];
-    if (kkt0_fth)
-      for (int j = 0; j < nt; ++j)
-        kkt0_fth[(size_t)r * nt + j] = Ft[(size_t)rd * NT + j];
-  }
-  for (int j = 0; j < nt; ++j) {
-    if (thGrad)
-      thGrad[j] = g[(size_t)j];
-    if (thHess)
-      std::memcpy(thHess + (size_t)j * nt, &H[(size_t)j * NT], sizeof(double) * (size_t)nt);
-  }
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  take_gains(kkt0_ff, rec.data(), false, n0, 1, rows, 1);
+  take_gains(kkt0_fth, rec.data() + o_fth, false, n0, NT, rows, nt);
+  if (thGrad)
+    take_block(thGrad, BlockMap{nt, 1, NT, 1, o_g, 0, 0.0, kFull}, rec.data());
+  if (thHess)
+    take_block(thHess, BlockMap{nt, nt, NT, NT, o_H, 0, 0.0, kFull}, rec.data());
   return GAR_HIP_OK;
 }
 

@@ -565,6 +565,7 @@ __global__ void __launch_bounds__(256) gar_store_to_host(double *dst_host, const
 // (fb ROW-major, riccati-kernel.hpp:96-97; the specialised kernel families keep it in the fbT2
 // device order) so that the host needs ONE copy instead of 2(N+1).  grid (N+1), 256 threads.
 // goff[2t], goff[2t+1]: offsets of stage t inside ff_all / fb_all.
+// (The host's statement of the same fbT2 and row rules: gar_record_io.hpp, gain_at / RowMap.)
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) gar_gather_gains(const gar_stage_meta *meta, const double *fac,
                                                         double *ff_all, double *fb_all,
@@ -599,6 +600,7 @@ __global__ void __launch_bounds__(256) gar_gather_gains(const gar_stage_meta *me
 // knot takes Q, q, C, d only (:787-797); G0 = init Jx, g0 = init value, and stage 0's Q gets the
 // initial condition's Hessian (:799-804).  Same order of additions as the reference.  HBM-bound:
 // one read and one write of a knot record per stage.
+// (The host's statement of the same record rules -- packed Q / R, padding -- is gar_record_io.hpp.)
 // ---------------------------------------------------------------------------
 struct UpdateParams {
   const gar_stage_meta *meta;
@@ -679,7 +681,8 @@ __global__ void __launch_bounds__(256) gar_update_lq(UpdateParams P) {
 // dimensions (unx, unu; uniform, unconstrained -- what a padded solver is), the knot records the device's (NX, NU).
 // Real rows / columns: the reference's sums in the reference's order, as above; the dummy controls get R = I, S = 0,
 // B = 0, r = 0, the dummy states Q = I, A = 0, f = 0, q = 0 and the extra rows [0 -I] x0 = 0 of the initial
-// constraint -- exactly what gar_hip_upload_stage / gar_hip_set_init write.  deriv_off / d_G0 / d_g0 / d_iH: the
+// constraint -- exactly what gar_hip_upload_stage / gar_hip_set_init write (gar_record_io.hpp: knot_block_maps,
+// init_block_maps, put_block).  deriv_off / d_G0 / d_g0 / d_iH: the
 // CALLER's derivative layout; unc0 rows of the caller's G0.
 __global__ void __launch_bounds__(256) gar_update_lq_padded(UpdateParams P, int unx, int unu, int unc0) {
   const int t = (int)blockIdx.x, b = (int)blockIdx.y, tid = (int)threadIdx.x;

@@ -7,9 +7,6 @@
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
-#if defined(__SSE2__)
-#include <emmintrin.h>
-#endif
 
 #include <algorithm>
 #include <atomic>
@@ -38,6 +35,7 @@
 #include "gar_leg_seg.hpp"
 #include "gar_kkt.hpp"
 #include "gar_host.hpp"
+#include "gar_record_io.hpp"
 
 namespace gar { // instantiated in gar_wave_sweep.cpp (its own translation unit, its own code-generation flags)
 #define GAR_SWEEP_EXTERN(NX, NU)                                                                                        \
@@ -480,13 +478,6 @@ gar::GenericParams make_params(gar_hip_solver *s, double mueq) {
   return P;
 }
 
-// non-temporal stores (stage_copy) are weakly ordered: make them globally visible before a DMA engine reads them
-inline void stage_fence() {
-#if defined(__SSE2__) && !defined(__HIP_DEVICE_COMPILE__)
-  _mm_sfence();
-#endif
-}
-
 void mark_dirty(gar_hip_solver *s, int b, int64_t lo, int64_t hi) {
   auto &iv = s->buf.dirty_iv[(size_t)b];
   // the common pattern is "append right after the last range" (knot after knot): O(1); gaps of
@@ -550,52 +541,6 @@ int commit(gar_hip_solver *s) {
   return GAR_HIP_OK;
 }
 
-// Host copy into the pinned staging area with non-temporal stores: the destination is written once and next read by
-// the DMA engine, so it should not be pulled into (read-for-ownership) nor left in the caches of the packing core --
-// a third less memory traffic than memcpy's cached stores on the 19 MB of a (56, 22), N = 256 problem (measured on
-// the GPU box's host: 920 -> 560 us).  Only for problems that do not fit the last-level cache next to their source
-// (gar_hip_solver::stage_nt): the 7.6 MB of the north-star problem pack at cache speed with plain stores (150 us
-// against 440 us with non-temporal ones).
-inline void stage_copy(double *dst, const double *src, size_t n, bool nt) {
-#if defined(__SSE2__) && !defined(__HIP_DEVICE_COMPILE__)
-  if (nt && n >= 512) {
-    size_t i = 0;
-    if (reinterpret_cast<uintptr_t>(dst) & 15) // 8-byte aligned at least: one scalar brings it to 16
-      dst[i] = src[i], ++i;
-    for (; i + 8 <= n; i += 8) {
-      const __m128d a = _mm_loadu_pd(src + i), b = _mm_loadu_pd(src + i + 2), c = _mm_loadu_pd(src + i + 4),
-                    d = _mm_loadu_pd(src + i + 6);
-      _mm_stream_pd(dst + i, a);
-      _mm_stream_pd(dst + i + 2, b);
-      _mm_stream_pd(dst + i + 4, c);
-      _mm_stream_pd(dst + i + 6, d);
-    }
-    for (; i < n; ++i)
-      dst[i] = src[i];
-    return;
-  }
-#endif
-  std::memcpy(dst, src, sizeof(double) * n);
-}
-
-// Lower triangle of an r x r column-major block `src` (null: zeros), packed (gar_layout.h: gar_lower_index) as
-// the lower triangle of an R x R block, R >= r, with `diag` on the diagonal beyond r: `dst` gets R (R + 1) / 2 doubles
-inline void pack_lower(double *dst, const double *src, int r, int R, double diag) {
-  for (int j = 0; j < R; ++j) {
-    double *col = dst + gar_lower_index(R, j, j);
-    const int n = R - j;
-    if (j < r && src) {
-      std::memcpy(col, src + (size_t)j * r + j, sizeof(double) * (size_t)(r - j));
-      if (R > r)
-        std::memset(col + (r - j), 0, sizeof(double) * (size_t)(R - r));
-    } else {
-      std::memset(col, 0, sizeof(double) * (size_t)n);
-      if (j >= r)
-        col[0] = diag;
-    }
-  }
-}
-
 // pipeline the upload: once the range being appended to has grown past 1 MiB it goes out
 // (asynchronously, pinned -> HBM) while the caller packs the next knots -- one Newton
 // iteration's 7.6 MB of knots then costs max(host packing, PCIe), not their sum
@@ -612,23 +557,30 @@ int flush_if_grown(gar_hip_solver *s, int b) {
   return GAR_HIP_OK;
 }
 
-int write_block(gar_hip_solver *s, int b, int64_t off, const double *src, int64_t n) {
-  if (n <= 0)
+// The n blocks `maps` (gar_record_io.hpp) of problem b, taken from `src`, into the `doubles` of its record that start at
+// `base`.  Staged: straight into the pinned record, which then is ONE dirty range -- the holes that packed triangles
+// leave inside their blocks included: block-by-block ranges would not merge, and a problem would go out as two small
+// copies per knot instead of 1 MiB pieces.  Unstaged (a staging area beyond 1 GiB): the same put_block into per-thread
+// scratch, then block by block to the device.
+int write_blocks(gar_hip_solver *s, int b, int64_t base, int64_t doubles, const BlockMap *maps, const double *const *src,
+                 int n) {
+  if (doubles <= 0)
     return GAR_HIP_OK;
+  thread_local std::vector<double> scratch;
+  if (!s->buf.staged)
+    scratch.resize((size_t)doubles);
+  double *rec = s->buf.staged ? s->buf.h_prob + (int64_t)b * s->prob_doubles + base : scratch.data();
+  for (int i = 0; i < n; ++i)
+    put_block(rec, maps[i], src[i], s->buf.staged && s->buf.stage_nt);
   if (s->buf.staged) {
-    double *dst = s->buf.h_prob + (int64_t)b * s->prob_doubles + off;
-    if (src)
-      stage_copy(dst, src, (size_t)n, s->buf.stage_nt);
-    else
-      std::memset(dst, 0, sizeof(double) * (size_t)n);
-    mark_dirty(s, b, off, off + n);
+    mark_dirty(s, b, base, base + doubles);
     return flush_if_grown(s, b);
   }
-  double *dst = s->buf.d_prob + (int64_t)b * s->prob_doubles + off;
-  if (src)
-    HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s->stream));
-  else
-    HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double) * (size_t)n, s->stream));
+  double *dev = s->buf.d_prob + (int64_t)b * s->prob_doubles + base;
+  for (int i = 0; i < n; ++i)
+    if (maps[i].doubles() > 0)
+      HIP_TRY(hipMemcpyAsync(dev + maps[i].off, rec + maps[i].off, sizeof(double) * (size_t)maps[i].doubles(),
+                             hipMemcpyHostToDevice, s->stream));
   return GAR_HIP_OK;
 }
 
@@ -874,48 +826,21 @@ int allocate(gar_hip_solver *s) {
 
 } // namespace
 
-// ---- padding helpers (gar_hip_solver::padded) ------------------------------------------------------------------
+// ---- padding helpers (gar_hip_solver::padded; the block rules: gar_record_io.hpp) -------------------------------
 namespace {
-// r x c column-major `src` (null: zeros) into the top-left corner of an R x C column-major block; `diag` on the
-// part of the diagonal beyond (r, c)
-const double *padded_block(std::vector<double> &buf, const double *src, int r, int c, int R, int C, double diag) {
-  buf.assign((size_t)R * C, 0.0);
-  if (src)
-    for (int j = 0; j < c; ++j)
-      std::memcpy(&buf[(size_t)j * R], src + (size_t)j * r, sizeof(double) * (size_t)r);
-  if (diag != 0.0)
-    for (int i = std::min(r, c); i < std::min(R, C); ++i)
-      buf[(size_t)i * R + i] = diag;
-  return buf.data();
-}
-// the leading r x r part of a symmetric R x R block stored as its packed lower triangle (gar_layout.h), as a full
-// column-major r x r block (both triangles)
-void unpack_lower(double *dst, const double *src, int r, int R) {
-  for (int j = 0; j < r; ++j)
-    for (int i = j; i < r; ++i)
-      dst[(size_t)j * r + i] = dst[(size_t)i * r + j] = src[gar_lower_index(R, i, j)];
-}
-// rows [0, unu) and [NU, NU + unx) of a gain block with NU + NX (+...) rows: the real controls and states
-inline int gain_row(const gar_hip_solver *s, int r, int nu_dev) {
-  const int unu = nu_dev > 0 ? s->unu : 0;
-  return r < unu ? r : r - unu + nu_dev;
-}
 // the caller's solution arrays out of one device solution record
 void strip_solution(const gar_hip_solver *s, const double *rec, double *xs, double *us, double *vs, double *lbdas) {
-  const int N = s->horizon, nx = s->unx;
+  const int N = s->horizon, nx = s->unx, nu = s->unu, nc0 = s->user_nc0;
   (void)vs; // padding applies to unconstrained problems only
+  auto take = [rec](double *dst, int n, int64_t off) { take_block(dst, BlockMap{n, 1, n, 1, off, 0, 0.0, kFull}, rec); };
   for (int t = 0; t <= N; ++t) {
     const gar_stage_meta &m = s->meta[t];
     if (xs)
-      std::memcpy(xs + (size_t)t * nx, rec + m.x_off, sizeof(double) * (size_t)nx);
+      take(xs + (size_t)t * nx, nx, m.x_off);
     if (us && m.nu > 0)
-      std::memcpy(us + (size_t)t * s->unu, rec + m.u_off, sizeof(double) * (size_t)s->unu);
-    if (lbdas) {
-      if (t == 0)
-        std::memcpy(lbdas, rec + m.l_off, sizeof(double) * (size_t)s->user_nc0);
-      else
-        std::memcpy(lbdas + s->user_nc0 + (size_t)(t - 1) * nx, rec + m.l_off, sizeof(double) * (size_t)nx);
-    }
+      take(us + (size_t)t * nu, nu, m.u_off);
+    if (lbdas)
+      take(t == 0 ? lbdas : lbdas + nc0 + (size_t)(t - 1) * nx, t == 0 ? nc0 : nx, m.l_off);
   }
 }
 // one device solution record -> the caller's record layout (ulay)
@@ -927,10 +852,6 @@ void strip_solution_rec(const gar_hip_solver *s, const double *dev, double *rec)
 
 static int fetch_results_impl(gar_hip_solver *s, int b, int what, int t_lo, int t_hi, double *gains_base, bool sync);
 static int prefetch_impl(gar_hip_solver *s, int b);
-static int upload_stage_impl(gar_hip_solver *s, int b, int t, const double *Q, const double *S, const double *R,
-                             const double *q, const double *r, const double *A, const double *B, const double *f,
-                             const double *C, const double *D, const double *d, const double *Gth, const double *Gx,
-                             const double *Gu, const double *Gv, const double *gamma);
 // (see gar_hip_solver::term_grown) the caller's dimensions as the library keeps them
 void normalise_terminal(gar_hip_solver *s) {
   const int N = s->horizon;
@@ -1220,98 +1141,20 @@ int gar_hip_init_offsets(const gar_hip_solver *s, int64_t out[2]) {
   return GAR_HIP_OK;
 }
 
-static int upload_stage_dev(gar_hip_solver *s, int b, int t, const double *Q, const double *S,
-                         const double *R, const double *q, const double *r, const double *A,
-                         const double *B, const double *f, const double *C, const double *D,
-                         const double *d, const double *Gth, const double *Gx,
-                         const double *Gu, const double *Gv, const double *gamma) {
-  const gar_stage_meta &m = s->meta[t];
-  const int nth_st = (m.flags & GAR_KNOT_HAS_PARAM) ? m.nth : 0;
-  const gar_knot_offsets o = gar_knot_layout(m.nx, m.nu, m.nc, m.nx2, nth_st);
-  const int64_t base = m.in_off;
-  const int nx = m.nx, nu = m.nu, nc = m.nc, nx2 = m.nx2;
-  if (!Q || !q || !A || !f || (nu > 0 && (!S || !R || !r || !B)))
-    return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_stage: null block");
-  int rc = 0;
-  // staged: the blocks are copied into the pinned record and the KNOT becomes one dirty range (the holes the packed
-  // triangles of Q and R leave inside their blocks included: block-by-block ranges would not merge, and a problem
-  // would go out as two small copies per knot instead of 1 MiB pieces)
-  auto put = [&](int64_t off, const double *src, int64_t n) {
-    if (n <= 0)
-      return;
-    if (!s->buf.staged) {
-      rc |= write_block(s, b, off, src, n);
-      return;
-    }
-    double *dst = s->buf.h_prob + (int64_t)b * s->prob_doubles + off;
-    if (src)
-      stage_copy(dst, src, (size_t)n, s->buf.stage_nt);
-    else
-      std::memset(dst, 0, sizeof(double) * (size_t)n);
-  };
-  if (s->qr_packed && t < s->horizon) { // Q, R: their lower triangles, packed, in the first n (n + 1) / 2 doubles of the block
-    if (s->buf.staged) {
-      double *rec = s->buf.h_prob + (int64_t)b * s->prob_doubles + base;
-      pack_lower(rec + o.Q, Q, nx, nx, 0.0);
-      pack_lower(rec + o.R, R, nu, nu, 0.0);
-    } else {
-      thread_local std::vector<double> pq, pr;
-      pq.resize((size_t)nx * (nx + 1) / 2);
-      pr.resize((size_t)nu * (nu + 1) / 2);
-      pack_lower(pq.data(), Q, nx, nx, 0.0);
-      pack_lower(pr.data(), R, nu, nu, 0.0);
-      put(base + o.Q, pq.data(), (int64_t)pq.size());
-      put(base + o.R, pr.data(), (int64_t)pr.size());
-    }
-  } else {
-    put(base + o.Q, Q, (int64_t)nx * nx);
-    put(base + o.R, R, (int64_t)nu * nu);
-  }
-  put(base + o.S, S, (int64_t)nx * nu);
-  put(base + o.q, q, nx);
-  put(base + o.r, r, nu);
-  put(base + o.A, A, (int64_t)nx2 * nx);
-  put(base + o.B, B, (int64_t)nx2 * nu);
-  put(base + o.f, f, nx2);
-  put(base + o.C, C, (int64_t)nc * nx);
-  put(base + o.D, D, (int64_t)nc * nu);
-  put(base + o.d, d, nc);
-  if (nth_st > 0) {
-    put(base + o.Gth, Gth, (int64_t)nth_st * nth_st);
-    put(base + o.Gx, Gx, (int64_t)nx * nth_st);
-    put(base + o.Gu, Gu, (int64_t)nu * nth_st);
-    put(base + o.Gv, Gv, (int64_t)nc * nth_st);
-    put(base + o.gamma, gamma, nth_st);
-  }
-  if (s->buf.staged) {
-    mark_dirty(s, b, base, base + gar_knot_doubles(nx, nu, nc, nx2, nth_st));
-    return flush_if_grown(s, b);
-  }
-  return rc ? GAR_HIP_ERR_DEVICE : GAR_HIP_OK;
-}
-
-static int set_init_dev(gar_hip_solver *s, int b, const double *G0, const double *g0) {
-  if (s->nc0 > 0 && (!G0 || !g0))
-    return fail(GAR_HIP_ERR_ARG, "gar_hip_set_init: null block");
-  int rc = write_block(s, b, s->G0_off, G0, (int64_t)s->nc0 * s->nx0);
-  rc |= write_block(s, b, s->g0_off, g0, s->nc0);
-  return rc ? GAR_HIP_ERR_DEVICE : GAR_HIP_OK;
-}
-
 int gar_hip_upload_packed(gar_hip_solver *s, int b0, int nb, const double *packed) {
   GAR_GUARD(s);
-  GAR_MULTI(s, multi_upload_packed(s, b0, nb, packed));
   if (!s || !packed || b0 < 0 || nb < 0 || b0 + nb > s->batch)
     return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_packed: bad argument");
-  if (s->padded || s->qr_packed) { // the caller's records: knot by knot through the padding / packing path
+  // The device's records differ from the caller's (padding, packed triangles of Q / R): knot by knot through
+  // gar_hip_upload_stage, which routes to the stage's owner on a multi-device solver.  (A padded solver is unconstrained
+  // and unparameterised; one that only packs Q / R may carry both.)
+  if (s->padded || s->qr_packed) {
     const gar::HostLayout &u = caller_layout(s);
     for (int b = b0; b < b0 + nb; ++b) {
       const double *rec = packed + (int64_t)(b - b0) * u.prob_doubles;
       for (int t = 0; t <= s->horizon; ++t) {
-        // (a padded solver is unconstrained and unparameterised; one that only packs Q / R may carry both)
         const gar_stage_meta &m = u.meta[t];
-        const int nth_st = (m.flags & GAR_KNOT_HAS_PARAM) ? m.nth : 0;
-        const gar_knot_offsets o = gar_knot_layout(m.nx, m.nu, m.nc, m.nx2, nth_st);
+        const gar_knot_offsets o = gar_knot_layout(m.nx, m.nu, m.nc, m.nx2, (m.flags & GAR_KNOT_HAS_PARAM) ? m.nth : 0);
         const double *k = rec + m.in_off;
         if (int rc = gar_hip_upload_stage(s, b, t, k + o.Q, k + o.S, k + o.R, k + o.q, k + o.r, k + o.A, k + o.B, k + o.f,
                                           k + o.C, k + o.D, k + o.d, k + o.Gth, k + o.Gx, k + o.Gu, k + o.Gv, k + o.gamma))
@@ -1322,6 +1165,7 @@ int gar_hip_upload_packed(gar_hip_solver *s, int b0, int nb, const double *packe
     }
     return GAR_HIP_OK;
   }
+  GAR_MULTI(s, multi_upload_packed(s, b0, nb, packed)); // (each device its own range of the records)
   const size_t bytes = sizeof(double) * (size_t)s->prob_doubles * nb;
   if (s->buf.staged) {
     std::memcpy(s->buf.h_prob + (int64_t)b0 * s->prob_doubles, packed, bytes);
@@ -1859,51 +1703,6 @@ static int get_solution_dev(gar_hip_solver *s, int b, double *xs, double *us, do
   return GAR_HIP_OK;
 }
 
-static int get_gains_dev(gar_hip_solver *s, int b, int t, double *ff, double *fb, double *fth) {
-  if (int rc = ensure_expanded(s))
-    return rc;
-  const gar_stage_meta &m = s->meta[t];
-  const int nx2r = s->dense ? 2 * m.nx2 : m.nx2; // stage-dense solver: rows [K; Z; L; Y]
-  const gar_factor_offsets o = gar_factor_layout(m.nx, m.nu, m.nc, nx2r, m.nth);
-  const double *rec = s->buf.d_fac + (int64_t)b * s->fac_doubles + m.fac_off;
-  const int64_t nr = (int64_t)m.nu + m.nc + nx2r;
-  int rc = d2h(s, ff, rec + o.ff, nr);
-  std::vector<double> tmp;
-  // the specialised kernel families keep fb (and fth) in the fbT2 device order
-  const bool t2 = records_t2(s, b) && t < s->horizon;
-  const bool fbt2 = t2 && fb;
-  const bool ftht2 = t2 && fth && m.nth > 0;
-  std::vector<double> tmpth;
-  if (fbt2) {
-    tmp.resize((size_t)(nr * m.nx));
-    rc |= d2h(s, tmp.data(), rec + o.fb, nr * m.nx);
-  } else {
-    rc |= d2h(s, fb, rec + o.fb, nr * m.nx);
-  }
-  if (ftht2) {
-    tmpth.resize((size_t)(nr * m.nth));
-    rc |= d2h(s, tmpth.data(), rec + o.fth, nr * m.nth);
-  } else {
-    rc |= d2h(s, fth, rec + o.fth, nr * m.nth);
-  }
-  if (rc)
-    return rc;
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  if (ftht2) {
-    const int NW = (int)nr, NT = m.nth;
-    for (int r = 0; r < NW; ++r)
-      for (int j = 0; j < NT; ++j)
-        fth[(size_t)r * NT + j] = tmpth[(size_t)(j >> 1) * (2 * NW) + 2 * r + (j & 1)];
-  }
-  if (fbt2) { // back to StageFactor's row-major [K; Z; Aff] (riccati-kernel.hpp:96-97)
-    const int NW = (int)nr, NX = m.nx;
-    for (int r = 0; r < NW; ++r)
-      for (int j = 0; j < NX; ++j)
-        fb[(size_t)r * NX + j] = tmp[(size_t)(j >> 1) * (2 * NW) + 2 * r + (j & 1)];
-  }
-  return GAR_HIP_OK;
-}
-
 int gar_hip_gains_doubles(const gar_hip_solver *s, int64_t out[2]) {
   if (!s || !out)
     return fail(GAR_HIP_ERR_ARG, "bad argument");
@@ -2085,87 +1884,6 @@ int gar_hip_get_gains_all(gar_hip_solver *s, int b, double *ff_all, double *fb_a
   return GAR_HIP_OK;
 }
 
-static int get_value_dev(gar_hip_solver *s, int b, int t, double *Vxx, double *vx, double *Vxt,
-                      double *Vtt, double *vt) {
-  if (int rc = ensure_expanded(s))
-    return rc;
-  const gar_stage_meta &m = s->meta[t];
-  const gar_factor_offsets o = gar_factor_layout(m.nx, m.nu, m.nc, s->dense ? 2 * m.nx2 : m.nx2, m.nth);
-  const double *rec = s->buf.d_fac + (int64_t)b * s->fac_doubles + m.fac_off;
-  std::vector<double> packed; // the serial one-wave family keeps the lower triangle, packed (gar_layout.h)
-  int rc = 0;
-  if (s->vxx_packed && Vxx) {
-    packed.resize((size_t)gar_sym_packed_doubles(m.nx));
-    rc = d2h(s, packed.data(), rec + o.Vxx, (int64_t)packed.size());
-  } else {
-    rc = d2h(s, Vxx, rec + o.Vxx, (int64_t)m.nx * m.nx);
-  }
-  rc |= d2h(s, vx, rec + o.vx, m.nx);
-  rc |= d2h(s, Vxt, rec + o.Vxt, (int64_t)m.nx * m.nth);
-  rc |= d2h(s, Vtt, rec + o.Vtt, (int64_t)m.nth * m.nth);
-  rc |= d2h(s, vt, rec + o.vt, m.nth);
-  if (rc)
-    return rc;
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  if (!packed.empty())
-    for (int j = 0; j < m.nx; ++j)
-      for (int i = 0; i < m.nx; ++i)
-        Vxx[(size_t)j * m.nx + i] = packed[(size_t)gar_sym_index(1, m.nx, i, j)];
-  return GAR_HIP_OK;
-}
-
-static int get_kkt_dev(gar_hip_solver *s, int b, int t, double mueq, double *out) {
-  if (s->dense)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, "kktMat of the stage-dense solver is not kept (the whole stage matrix: gar_dense.hpp)");
-  if (!out)
-    return fail(GAR_HIP_ERR_ARG, "null output");
-  if (int rc = ensure_expanded(s))
-    return rc;
-  const gar_stage_meta &m = s->meta[t];
-  const int nk = m.nu + m.nc;
-  if (nk == 0)
-    return GAR_HIP_OK;
-  if ((int64_t)nk * nk > s->buf.kkt_doubles) {
-    s->buf.kkt_doubles = 0;
-    HIP_TRY(s->buf.d_kkt.alloc((size_t)nk * nk)); // (lets the smaller one go first)
-    s->buf.kkt_doubles = (int64_t)nk * nk;
-  }
-  if (commit(s) != GAR_HIP_OK)
-    return GAR_HIP_ERR_DEVICE;
-  const int nth_st = (m.flags & GAR_KNOT_HAS_PARAM) ? m.nth : 0;
-  const gar_knot_offsets ko = gar_knot_layout(m.nx, m.nu, m.nc, m.nx2, nth_st);
-  const double *knot = s->buf.d_prob + (int64_t)b * s->prob_doubles + m.in_off;
-  // the stage's value-function term: none at the terminal knot and at the last knot of a leg (each leg ends
-  // with terminalSolve, parallel-solver.hxx:150-160)
-  const double *Vn = nullptr;
-  if (t < s->horizon && !(m.flags & GAR_KNOT_LEG_END) && m.nu > 0) {
-    const gar_stage_meta &mn = s->meta[t + 1];
-    const gar_factor_offsets fn = gar_factor_layout(mn.nx, mn.nu, mn.nc, mn.nx2, mn.nth);
-    Vn = s->buf.d_fac + (int64_t)b * s->fac_doubles + mn.fac_off + fn.Vxx;
-  }
-  hipLaunchKernelGGL(gar::gar_kkt_matrix, dim3(1), dim3(256), 0, s->stream, knot, ko, Vn, m.nx2, m.nu, m.nc, mueq,
-                     s->buf.d_kkt.get(), s->vxx_packed ? 1 : 0, (s->qr_packed && t < s->horizon) ? 1 : 0);
-  HIP_TRY(hipGetLastError());
-  if (int rc = d2h(s, out, s->buf.d_kkt, (int64_t)nk * nk))
-    return rc;
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return GAR_HIP_OK;
-}
-
-static int get_initial_dev(gar_hip_solver *s, int b, double *kkt0_ff, double *kkt0_fth,
-                        double *thGrad, double *thHess) {
-  const double *io = s->buf.d_init + (int64_t)b * s->init_doubles;
-  const int64_t n0 = s->n0, nth = s->nth0;
-  int rc = d2h(s, kkt0_ff, io, n0);
-  rc |= d2h(s, kkt0_fth, io + n0, n0 * nth);
-  rc |= d2h(s, thGrad, io + n0 + n0 * nth, nth);
-  rc |= d2h(s, thHess, io + n0 + n0 * nth + nth, nth * nth);
-  if (rc)
-    return rc;
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return GAR_HIP_OK;
-}
-
 int gar_hip_debug_trace(gar_hip_solver *s, int enable, long long out[64]) {
   GAR_GUARD(s);
   if (!s)
@@ -2245,59 +1963,34 @@ int gar_hip_download_packed(gar_hip_solver *s, int b0, int nb, double *packed) {
     return fail(GAR_HIP_ERR_ARG, "gar_hip_download_packed: bad argument");
   if (int rc = commit(s))
     return rc;
-  if (s->padded) { // device records -> the caller's: the real rows / columns of every block
-    const gar::HostLayout &u = *s->ulay;
-    std::vector<double> dev((size_t)s->prob_doubles);
-    for (int b = b0; b < b0 + nb; ++b) {
-      HIP_TRY(hipMemcpyAsync(dev.data(), s->buf.d_prob + (int64_t)b * s->prob_doubles, sizeof(double) * dev.size(),
-                             hipMemcpyDeviceToHost, s->stream));
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      double *rec = packed + (int64_t)(b - b0) * u.prob_doubles;
-      std::memset(rec, 0, sizeof(double) * (size_t)u.prob_doubles);
-      auto take = [](double *dst, const double *src, int r, int c, int R) {
-        for (int j = 0; j < c; ++j)
-          std::memcpy(dst + (size_t)j * r, src + (size_t)j * R, sizeof(double) * (size_t)r);
-      };
-      take(rec + u.G0_off, dev.data() + s->G0_off, s->user_nc0, s->unx, s->nc0);
-      take(rec + u.g0_off, dev.data() + s->g0_off, s->user_nc0, 1, s->nc0);
-      for (int t = 0; t <= s->horizon; ++t) {
-        const gar_stage_meta &m = u.meta[t], &M = s->meta[t];
-        const gar_knot_offsets o = gar_knot_layout(m.nx, m.nu, 0, m.nx2, 0), O = gar_knot_layout(M.nx, M.nu, 0, M.nx2, 0);
-        double *k = rec + m.in_off;
-        const double *K = dev.data() + M.in_off;
-        if (s->qr_packed && t < s->horizon) {
-          unpack_lower(k + o.Q, K + O.Q, m.nx, M.nx);
-          unpack_lower(k + o.R, K + O.R, m.nu, M.nu);
-        } else {
-          take(k + o.Q, K + O.Q, m.nx, m.nx, M.nx);
-          take(k + o.R, K + O.R, m.nu, m.nu, M.nu);
-        }
-        take(k + o.S, K + O.S, m.nx, m.nu, M.nx);
-        take(k + o.q, K + O.q, m.nx, 1, M.nx);
-        take(k + o.r, K + O.r, m.nu, 1, M.nu);
-        take(k + o.A, K + O.A, m.nx2, m.nx, M.nx2);
-        take(k + o.B, K + O.B, m.nx2, m.nu, M.nx2);
-        take(k + o.f, K + O.f, m.nx2, 1, M.nx2);
-      }
-    }
+  if (!(s->padded || s->qr_packed)) { // the device's records are the caller's
+    HIP_TRY(hipMemcpyAsync(packed, s->buf.d_prob + (int64_t)b0 * s->prob_doubles,
+                           sizeof(double) * (size_t)s->prob_doubles * nb, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
     return GAR_HIP_OK;
   }
-  HIP_TRY(hipMemcpyAsync(packed, s->buf.d_prob + (int64_t)b0 * s->prob_doubles,
-                         sizeof(double) * (size_t)s->prob_doubles * nb, hipMemcpyDeviceToHost,
-                         s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  if (s->qr_packed) { // the device keeps the lower triangles of Q and R, packed: the full symmetric blocks back
-    std::vector<double> tmp;
-    for (int k = 0; k < nb; ++k)
-      for (int t = 0; t < s->horizon; ++t) {
-        const gar_stage_meta &m = s->meta[t];
-        const gar_knot_offsets o = gar_knot_layout(m.nx, m.nu, m.nc, m.nx2, 0);
-        double *rec = packed + (int64_t)k * s->prob_doubles + m.in_off;
-        for (const auto &blk : {std::make_pair(o.Q, m.nx), std::make_pair(o.R, m.nu)}) {
-          tmp.assign(rec + blk.first, rec + blk.first + (size_t)blk.second * (blk.second + 1) / 2);
-          unpack_lower(rec + blk.first, tmp.data(), blk.second, blk.second);
-        }
-      }
+  // device records -> the caller's, block by block (gar_record_io.hpp): the real rows / columns, both triangles of Q, R
+  const gar::HostLayout &u = caller_layout(s);
+  std::vector<double> dev((size_t)s->prob_doubles);
+  for (int b = b0; b < b0 + nb; ++b) {
+    HIP_TRY(hipMemcpyAsync(dev.data(), s->buf.d_prob + (int64_t)b * s->prob_doubles, sizeof(double) * dev.size(),
+                           hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    double *rec = packed + (int64_t)(b - b0) * u.prob_doubles;
+    if (s->padded) // (what lies between the blocks: zeros, or what the device holds there)
+      std::memset(rec, 0, sizeof(double) * (size_t)u.prob_doubles);
+    else
+      std::memcpy(rec, dev.data(), sizeof(double) * dev.size());
+    BlockMap maps[16];
+    init_block_maps(maps, u.nc0, u.nx0, s->nc0, s->nx0, s->G0_off, s->g0_off, u.G0_off, u.g0_off);
+    for (int i = 0; i < 2; ++i)
+      take_block(rec + maps[i].uoff, maps[i], dev.data());
+    for (int t = 0; t <= s->horizon; ++t) {
+      const gar_stage_meta &m = u.meta[t], &M = s->meta[t];
+      knot_block_maps(maps, m, M, (M.flags & GAR_KNOT_HAS_PARAM) ? M.nth : 0, s->qr_packed && t < s->horizon);
+      for (const BlockMap &blk : maps)
+        take_block(rec + m.in_off + blk.uoff, blk, dev.data() + M.in_off);
+    }
   }
   return GAR_HIP_OK;
 }

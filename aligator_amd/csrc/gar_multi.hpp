@@ -128,29 +128,11 @@ int upload_packed_range(gar_hip_solver *q, int b0, int nb, const double *packed,
   return GAR_HIP_OK;
 }
 
+// (gar_hip_upload_packed, whose arguments it has checked: records in the caller's format only -- neither padded nor
+// with packed triangles)
 int multi_upload_packed(gar_hip_solver *s, int b0, int nb, const double *packed) {
   gar_multi *M = s->multi;
-  if (!packed || b0 < 0 || nb < 0 || b0 + nb > s->batch)
-    return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_packed: bad argument");
   const int N = s->horizon;
-  if (s->padded) { // the caller's records, knot by knot through the padding path of the stage's owner
-    const gar::HostLayout &u = *s->ulay;
-    for (int b = b0; b < b0 + nb; ++b) {
-      const double *rec = packed + (int64_t)(b - b0) * u.prob_doubles;
-      for (int t = 0; t <= N; ++t) {
-        const gar_stage_meta &m = u.meta[t];
-        const gar_knot_offsets o = gar_knot_layout(m.nx, m.nu, 0, m.nx2, 0);
-        const double *k = rec + m.in_off;
-        if (int rc = gar_hip_upload_stage(M->subs[(size_t)M->owner[(size_t)t]], b, t, k + o.Q, k + o.S, k + o.R, k + o.q,
-                                          k + o.r, k + o.A, k + o.B, k + o.f, nullptr, nullptr, nullptr, nullptr,
-                                          nullptr, nullptr, nullptr, nullptr))
-          return rc;
-      }
-      if (int rc = multi_set_init(s, b, rec + u.G0_off, rec + u.g0_off))
-        return rc;
-    }
-    return GAR_HIP_OK;
-  }
   const int64_t head = s->meta[0].in_off; // G0 | g0
   for (size_t r = 0; r < M->subs.size(); ++r) {
     const int64_t lo = s->meta[(size_t)M->t_lo[r]].in_off;
