@@ -1432,9 +1432,17 @@ __global__ void __launch_bounds__(64, 1) gar_backward_wave(MfmaParams P, int bat
   gar_backward_wave_body<NX, NU, NC, 0>(P, batch);
 }
 // the same sweep under a name of its own for the HALF-batch launches of the pipelined schedule (gar_hip_set_pipeline):
-// a profile of a run that uses both schedules then lists the two launch populations apart
+// a profile of a run that uses both schedules then lists the two launch populations apart.
+// It is the POLE wave of that schedule: the step is the chain of the backward halves, and each shares its SIMD with a
+// gar_forward_lean wave that was enqueued ahead of it -- the older wave, which wins the issue arbitration at equal
+// priority.  One static s_setprio before the stage loop, no per-phase flips: priority 3 shortens the half by 1-2 % and
+// the step by 1.3 % (the roll-out beside it gets slower, 3.0 -> 3.5 ms, and stays off the chain); priority 1 measured
+// nothing (profiles/r07_*).  A scalar instruction: it changes no register (424 at (36, 12)).
 template <int NX, int NU>
 __global__ void __launch_bounds__(64, 1) gar_backward_wave_half(MfmaParams P, int batch) {
+#if defined(__HIP_DEVICE_COMPILE__) // (the emulator has no issue arbitration)
+  __builtin_amdgcn_s_setprio(3);
+#endif
   gar_backward_wave_body<NX, NU, 0, 0>(P, batch);
 }
 // The plain unconstrained shapes are instantiated ONCE, in gar_wave_sweep.cpp (a translation unit of its own: see
