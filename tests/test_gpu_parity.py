@@ -178,7 +178,9 @@ def test_constrained_bench_shape_full_factors_at_benchmark_size():
 def test_constrained_decoupled_dense_c_and_alternating_d():
     """D = 0 stages (gar_wave2.hpp, NC > 0) with a dense C, and sweeps that alternate between the decoupled
     stage and the (NU+NC) Bunch-Kaufman stage."""
-    pc.check_constrained_decoupled(shapes=((8, 4, 4, 25, 1e-6), (16, 8, 8, 30, 1e-8), (36, 12, 32, 40, 1e-8)))
+    # (horizon 41: the highest odd knot is N-2, so the benchmark shape too leaves the first kernel below N-1)
+    pc.check_constrained_decoupled(shapes=((8, 4, 4, 25, 1e-6), (16, 8, 8, 30, 1e-8), (36, 12, 32, 40, 1e-8),
+                                           (36, 12, 32, 41, 1e-8)))
 
 
 @pytest.mark.parametrize("nx,nu,nc,horz,mu", [(36, 12, 32, 40, 1e-6), (16, 8, 8, 30, 1e-8), (8, 4, 4, 25, 1e-5)])
