@@ -68,6 +68,11 @@ SIGNATURES = {
     "gar_hip_kkt_error": (C.c_int, [C.c_void_p, C.c_double, _PD, _PD, _PD]),
     "gar_hip_device_kkt_errors": (C.c_void_p, [C.c_void_p]),
     "gar_hip_device_kkt_stage_errors": (C.c_void_p, [C.c_void_p]),
+    "gar_hip_affine_doubles": (C.c_int64, [C.c_void_p]),
+    "gar_hip_upload_affine": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PD]),
+    "gar_hip_upload_affine_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "gar_hip_backward_affine": (C.c_int, [C.c_void_p]),
+    "gar_hip_backward_affine_async": (C.c_int, [C.c_void_p]),
     "gar_hip_slow_path_stages": (C.c_int, [C.c_void_p, _PI64]),
     "gar_hip_constrained_bk_stages": (C.c_int, [C.c_void_p, _PI64]),
     "gar_hip_boundary_doubles": (C.c_int64, [C.c_void_p]),

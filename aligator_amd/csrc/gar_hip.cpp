@@ -34,6 +34,7 @@
 #include "gar_cstr_seg_api.hpp"
 #include "gar_leg_seg.hpp"
 #include "gar_kkt.hpp"
+#include "gar_affine.hpp"
 #include "gar_host.hpp"
 #include "gar_record_io.hpp"
 
@@ -1166,6 +1167,7 @@ int gar_hip_upload_packed(gar_hip_solver *s, int b0, int nb, const double *packe
     return GAR_HIP_OK;
   }
   GAR_MULTI(s, multi_upload_packed(s, b0, nb, packed)); // (each device its own range of the records)
+  affine_invalidate(s, "gar_hip_upload_packed");
   const size_t bytes = sizeof(double) * (size_t)s->prob_doubles * nb;
   if (s->buf.staged) {
     std::memcpy(s->buf.h_prob + (int64_t)b0 * s->prob_doubles, packed, bytes);
@@ -1188,6 +1190,7 @@ int gar_hip_upload_packed_device(gar_hip_solver *s, int b0, int nb, const double
     return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_packed_device: bad argument");
   if (int rc = commit(s)) // staged host data first, then the device copy wins
     return rc;
+  affine_invalidate(s, "gar_hip_upload_packed_device");
   HIP_TRY(hipMemcpyAsync(s->buf.d_prob + (int64_t)b0 * s->prob_doubles, packed_dev,
                          sizeof(double) * (size_t)s->prob_doubles * nb, hipMemcpyDeviceToDevice,
                          s->stream));
@@ -1252,6 +1255,7 @@ int gar_hip_backward_legs_async(gar_hip_solver *s, double mueq) {
                                         " on constrained knots)");
   GAR_MULTI(s, multi_backward_legs(s, mueq));
   s->eager_fwd = false;
+  affine_note_backward(s, mueq);
   if (s->lazy.ev_pref) { // a read-back of the previous sweep's gains may still be in flight on the second stream
     HIP_TRY(hipStreamWaitEvent(s->stream, s->lazy.ev_pref, 0));
     s->pref_b = -1;
@@ -1649,6 +1653,74 @@ const double *gar_hip_device_kkt_stage_errors(gar_hip_solver *s) {
   return s && !s->multi ? s->buf.d_kkt_stage.get() : nullptr;
 }
 
+// ---- re-solve for new affine terms from the stored factorisation (gar_affine.hpp; launches in gar_launch.hpp) ---------
+int64_t gar_hip_affine_doubles(const gar_hip_solver *s) { return s && !s->user_dims5.empty() ? affine_offsets(s, nullptr) : 0; }
+
+int gar_hip_upload_affine_device(gar_hip_solver *s, int b0, int nb, const double *affine_dev) {
+  GAR_GUARD(s);
+  if (int rc = affine_check(s, "gar_hip_upload_affine_device"))
+    return rc;
+  if (!affine_dev || b0 < 0 || nb < 0 || b0 + nb > s->batch)
+    return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_affine_device: bad argument");
+  if (int rc = affine_buffers(s))
+    return rc;
+  return launch_affine_scatter(s, b0, nb, affine_dev);
+}
+
+int gar_hip_upload_affine(gar_hip_solver *s, int b0, int nb, const double *affine_host) {
+  GAR_GUARD(s);
+  if (int rc = affine_check(s, "gar_hip_upload_affine"))
+    return rc;
+  if (!affine_host || b0 < 0 || nb < 0 || b0 + nb > s->batch)
+    return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_affine: bad argument");
+  if (int rc = affine_buffers(s))
+    return rc;
+  const size_t n = (size_t)affine_offsets(s, nullptr);
+  if (n == 0 || nb == 0)
+    return GAR_HIP_OK;
+  if (!s->buf.d_aff_in)
+    HIP_TRY(s->buf.d_aff_in.alloc(n * (size_t)s->batch));
+  if (int rc = commit(s)) // (the pinned area is free once its staged blocks are on their way)
+    return rc;
+  // through the pinned staging area where there is one (a problem's record is longer than its affine vector)
+  const double *from = affine_host;
+  if (s->buf.staged) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    std::memcpy(s->buf.h_prob.get(), affine_host, sizeof(double) * n * (size_t)nb);
+    from = s->buf.h_prob;
+  }
+  HIP_TRY(hipMemcpyAsync(s->buf.d_aff_in.get(), from, sizeof(double) * n * (size_t)nb, hipMemcpyHostToDevice, s->stream));
+  if (int rc = launch_affine_scatter(s, b0, nb, s->buf.d_aff_in))
+    return rc;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return GAR_HIP_OK;
+}
+
+int gar_hip_backward_affine_async(gar_hip_solver *s) {
+  GAR_GUARD(s); // (a pipelined sweep: the solver's stream is ordered behind the half streams first)
+  if (int rc = affine_check(s, "gar_hip_backward_affine"))
+    return rc;
+  if (!s->buf.aff_ready)
+    return fail(GAR_HIP_ERR_ARG, s->buf.aff_stale ? std::string("gar_hip_backward_affine: matrix blocks changed since the last backward (") +
+                                                        s->buf.aff_stale + "): call gar_hip_backward first"
+                                                  : std::string("gar_hip_backward_affine: no backward of this solver to re-solve from"));
+  if (int rc = affine_buffers(s))
+    return rc;
+  return launch_backward_affine(s);
+}
+
+int gar_hip_backward_affine(gar_hip_solver *s) {
+  GAR_GUARD(s);
+  if (int rc = gar_hip_backward_affine_async(s))
+    return rc;
+  const int nf = gar_hip_num_failed(s);
+  if (nf < 0)
+    return fail(GAR_HIP_ERR_DEVICE, std::string("backward_affine: ") + hipGetErrorString(hipGetLastError()));
+  if (nf > 0)
+    return fail(GAR_HIP_ERR_FACTOR, "Failed stage LDL factorization (" + std::to_string(nf) + " problem(s))");
+  return GAR_HIP_OK;
+}
+
 int gar_hip_get_status(gar_hip_solver *s, int32_t *out) {
   GAR_GUARD(s);
   if (!s || !out)
@@ -1923,6 +1995,7 @@ int gar_hip_update_lq_subproblem_device(gar_hip_solver *s, const double *deriv_d
   GAR_MULTI(s, fail(GAR_HIP_ERR_UNSUPPORTED, "device-resident LQ assembly on a multi-device solver: one derivative buffer per device would be needed"));
   if (int rc = commit(s)) // pending host staging first; later host writes flush only their own ranges
     return rc;
+  affine_invalidate(s, "gar_hip_update_lq_subproblem_device");
   const gar::HostLayout &u = caller_layout(s); // the layout of the derivative buffer: the caller's dimensions
   if (!s->buf.d_deriv_off) {
     HIP_TRY(s->buf.d_deriv_off.alloc(u.deriv_off.size()));
@@ -2071,6 +2144,7 @@ int gar_hip_cycle_append(gar_hip_solver *s, const int32_t d[5]) {
     HIP_TRY(hipEventSynchronize(s->lazy.ev_pref));
   s->pref_b = -1;
   s->eager_fwd = false;
+  affine_invalidate(s, "gar_hip_cycle_append");
   const int N = s->horizon;
   if (N < 1)
     return GAR_HIP_OK;

@@ -248,6 +248,18 @@ struct LayoutState {
   // the first call or neither; the LDS one workgroup of gar_kkt_stage_residuals asks for (bytes)
   DevBuf<double> d_kkt_stage, d_kkt_err;
   size_t kkt_lds_bytes = 0;
+  // gar_hip_backward_affine (gar_affine.hpp), all on the first call or none: W = Rhat^-1 [batch][horizon + 1][aff_w_rec],
+  // the "re-solved" flags [batch], the offsets of the caller's affine vector [horizon + 2]; the host upload's device
+  // staging (batch vectors) on ITS first call.  aff_ready: a backward has left factor records and no matrix block was
+  // uploaded since (aff_stale names what was); aff_W_valid: W belongs to those records
+  DevBuf<double> d_aff_W, d_aff_in;
+  DevBuf<int> d_aff_ok;
+  DevBuf<long long> d_aff_off;
+  int aff_w_rec = 0, aff_nx_max = 0;
+  size_t aff_lds_bytes = 0, aff_prep_lds_bytes = 0;
+  bool aff_ready = false, aff_W_valid = false;
+  double aff_mueq = 0.0;
+  const char *aff_stale = nullptr;
 };
 
 // Solver lifetime: the pipelined sweep's half streams and events (gar_hip_set_pipeline; the serial one-wave family,

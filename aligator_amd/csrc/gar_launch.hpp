@@ -9,6 +9,20 @@ inline hipError_t stamp(gar_hip_solver *s, int i, bool when = true) {
   return s->timing && when ? hipEventRecord(s->lazy.ev[i], s->stream) : hipSuccess;
 }
 
+// gar_hip_backward_affine's state (gar_hip.h): every backward leaves factor records to re-solve from and makes W stale;
+// an upload of matrix blocks (or a cycleAppend) leaves nothing to re-solve from until the next backward
+inline void affine_note_backward(gar_hip_solver *s, double mueq) {
+  s->buf.aff_ready = true;
+  s->buf.aff_W_valid = false;
+  s->buf.aff_mueq = mueq;
+  s->buf.aff_stale = nullptr;
+}
+inline void affine_invalidate(gar_hip_solver *s, const char *cause) {
+  if (s->buf.aff_ready || s->buf.aff_stale) // (before the first backward there is nothing to make stale)
+    s->buf.aff_stale = cause;
+  s->buf.aff_ready = s->buf.aff_W_valid = false;
+}
+
 // MfmaParams of a stage sweep over the caller's knots: mfma_common + where the factor records go, mueq and the
 // per-launch GAR_HIP_SPD_ACCEPT.  Called as it is, this is the scratch-record form of the segment legs and the constrained
 // segment legs (fac = d_fac2): trace, init, init_stride, G0_off, g0_off, nc0, init_closed and ring0 stay ZERO there on
@@ -608,6 +622,156 @@ int launch_kkt(gar_hip_solver *s, double mueq, const double *theta_dev) {
   hipLaunchKernelGGL(gar::gar_kkt_stage_residuals, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)),
                      dim3(GAR_KKT_THREADS), s->buf.kkt_lds_bytes, s->stream, K);
   hipLaunchKernelGGL(gar::gar_kkt_reduce, dim3((unsigned)s->batch), dim3(64), 0, s->stream, K);
+  HIP_TRY(hipGetLastError());
+  return GAR_HIP_OK;
+}
+
+// ---- the re-solve for new affine terms (gar_affine.hpp): scatter, prepare, the vector sweep, the initial stage -----------
+// doubles of one problem's affine vector and the offsets of its stages (q_t | r_t | f_t ... g0), the CALLER's dimensions;
+// a terminal knot given with nx2 = 0 has no f
+int64_t affine_offsets(const gar_hip_solver *s, std::vector<long long> *off) {
+  const int N = s->horizon;
+  long long p = 0;
+  if (off)
+    off->assign((size_t)N + 2, 0);
+  for (int t = 0; t <= N; ++t) {
+    const int32_t *d = &s->user_dims5[5 * (size_t)t];
+    if (off)
+      (*off)[(size_t)t] = p;
+    p += d[0] + d[1] + ((s->term_grown && t == N) ? 0 : d[3]);
+  }
+  if (off)
+    (*off)[(size_t)N + 1] = p;
+  return p + s->user_nc0;
+}
+
+// who is served: serial in time, one device, nc = nth = 0 on every knot, the stand-alone initial stage of one wave
+int affine_check(const gar_hip_solver *s, const char *who) {
+  if (!s)
+    return fail(GAR_HIP_ERR_ARG, "null solver");
+  const std::string w(who);
+  if (s->multi)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, w + ": a multi-device solver is not served (the records live on several devices)");
+  if (s->dense)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, w + ": the stage-dense solver is not served");
+  if (s->num_legs != 1 || s->world != 1)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, w + ": leg mode is not served (num_legs = 1 only)");
+  if (s->fold)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, w + ": a folded solver (constrained knots) is not served");
+  for (int t = 0; t <= s->horizon; ++t) {
+    const int32_t *d = &s->dims5[5 * (size_t)t];
+    if (d[2] != 0 || d[4] != 0)
+      return fail(GAR_HIP_ERR_UNSUPPORTED, w + ": knot " + std::to_string(t) + " is constrained or parameterised (nc = nth = 0 only)");
+  }
+  if (s->n0 > 128)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, w + ": nx + nc0 above 128 (the stand-alone initial stage of one wave)");
+  return GAR_HIP_OK;
+}
+
+gar::AffineParams make_affine_params(gar_hip_solver *s) {
+  gar::AffineParams A{};
+  A.meta = s->buf.d_meta;
+  A.prob = s->buf.d_prob;
+  A.fac = s->buf.d_fac;
+  A.W = s->buf.d_aff_W;
+  A.status = status_words(s);
+  A.ok = s->buf.d_aff_ok;
+  A.src_off = s->buf.d_aff_off;
+  A.prob_stride = s->prob_doubles;
+  A.fac_stride = s->fac_doubles;
+  A.src_stride = affine_offsets(s, nullptr);
+  A.g0_off = s->g0_off;
+  A.horizon = s->horizon;
+  A.w_rec = s->buf.aff_w_rec;
+  A.unx = s->padded ? s->unx : 0;
+  A.unu = s->padded ? s->unu : 0;
+  A.unc0 = s->user_nc0;
+  A.qr_packed = s->qr_packed ? 1 : 0;
+  A.vxx_packed = s->vxx_packed ? 1 : 0;
+  A.fb_t2 = s->fb_t2 ? 1 : 0;
+  A.nx_max = s->buf.aff_nx_max;
+  return A;
+}
+
+// the side buffers, on the first call after the layout was built (all or none), and the two kernels' LDS
+int affine_buffers(gar_hip_solver *s) {
+  if (s->buf.d_aff_off)
+    return GAR_HIP_OK;
+  if ((int64_t)s->batch * (s->horizon + 1) > INT32_MAX)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_backward_affine: batch x (horizon + 1) above 2^31 - 1 workgroups");
+  int nu_max = 0, nx_max = 0, lds = 0, plds = 0;
+  for (const gar_stage_meta &m : s->meta) {
+    nu_max = std::max(nu_max, (int)m.nu);
+    nx_max = std::max(nx_max, std::max((int)m.nx, (int)m.nx2));
+  }
+  for (const gar_stage_meta &m : s->meta) {
+    lds = std::max(lds, gar::affine_sweep_lds_doubles(nx_max, m.nx, m.nu, m.nx2, s->fb_t2, s->vxx_packed));
+    plds = std::max(plds, gar::affine_prepare_lds_doubles(m.nu, m.nx2, s->vxx_packed));
+  }
+  if ((size_t)std::max(lds, plds) * sizeof(double) > kCuLdsBytes)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_backward_affine: a stage's blocks need " +
+                                             std::to_string((size_t)std::max(lds, plds) * sizeof(double)) + " B of LDS (> 160 KiB per CU)");
+  HIP_TRY(max_lds(gar::gar_backward_affine, (size_t)lds));
+  HIP_TRY(max_lds(gar::gar_affine_prepare, (size_t)plds));
+  std::vector<long long> off;
+  affine_offsets(s, &off);
+  const int w_rec = std::max(2, (nu_max * nu_max + 1) & ~1);
+  DevBuf<double> W;
+  DevBuf<int> ok;
+  DevBuf<long long> doff;
+  HIP_TRY(W.zalloc((size_t)s->batch * (size_t)(s->horizon + 1) * (size_t)w_rec));
+  HIP_TRY(ok.zalloc((size_t)s->batch));
+  HIP_TRY(doff.alloc(off.size()));
+  HIP_TRY(hipMemcpy(doff, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice));
+  s->buf.d_aff_W = std::move(W);
+  s->buf.d_aff_ok = std::move(ok);
+  s->buf.d_aff_off = std::move(doff);
+  s->buf.aff_w_rec = w_rec;
+  s->buf.aff_nx_max = nx_max;
+  s->buf.aff_lds_bytes = (size_t)lds * sizeof(double);
+  s->buf.aff_prep_lds_bytes = (size_t)plds * sizeof(double);
+  s->buf.aff_W_valid = false;
+  return GAR_HIP_OK;
+}
+
+// nb affine vectors at the DEVICE address src into the knots of problems b0 ..: staged host blocks go out first, so
+// that no later flush writes older q, r, f over these
+int launch_affine_scatter(gar_hip_solver *s, int b0, int nb, const double *src_dev) {
+  if (nb == 0)
+    return GAR_HIP_OK;
+  if (int rc = commit(s))
+    return rc;
+  gar::AffineParams A = make_affine_params(s);
+  A.src = src_dev;
+  A.b0 = b0;
+  hipLaunchKernelGGL(gar::gar_affine_scatter, dim3((unsigned)nb * (unsigned)(s->horizon + 1)), dim3(64), 0, s->stream, A);
+  HIP_TRY(hipGetLastError());
+  return GAR_HIP_OK;
+}
+
+int launch_backward_affine(gar_hip_solver *s) {
+  RoctxRange range_("gar::backward_affine");
+  s->eager_fwd = false;
+  if (s->lazy.ev_pref) { // a read-back of the previous sweep's gains may still be in flight on the second stream
+    HIP_TRY(hipStreamWaitEvent(s->stream, s->lazy.ev_pref, 0));
+    s->pref_b = -1;
+  }
+  if (int rc = commit(s)) // (a g0 staged through gar_hip_set_init)
+    return rc;
+  const gar::AffineParams A = make_affine_params(s);
+  if (!s->buf.aff_W_valid) {
+    hipLaunchKernelGGL(gar::gar_affine_prepare, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)), dim3(64),
+                       s->buf.aff_prep_lds_bytes, s->stream, A);
+    HIP_TRY(hipGetLastError());
+    s->buf.aff_W_valid = true;
+  }
+  hipLaunchKernelGGL(gar::gar_backward_affine, dim3((unsigned)s->batch), dim3(64), s->buf.aff_lds_bytes, s->stream, A);
+  // the initial stage: the stand-alone kernel backward_serial launches for the families that do not fuse it, on the
+  // problems the sweep took (kkt0 is factorised again: its matrix is not kept)
+  gar::GenericParams I = make_params(s, s->buf.aff_mueq);
+  I.only = s->buf.d_aff_ok;
+  hipLaunchKernelGGL(gar::gar_initial_wave, dim3((unsigned)s->batch), dim3(64),
+                     (size_t)gar::gar_initial_wave_lds_doubles(s->n0, s->nth0) * sizeof(double), s->stream, I);
   HIP_TRY(hipGetLastError());
   return GAR_HIP_OK;
 }

@@ -60,6 +60,7 @@ int pipe_fork(gar_hip_solver *s, bool again = false) {
 int pipe_backward(gar_hip_solver *s, double mueq) {
   RoctxRange range_("gar::backwardImpl+factor_initial (pipelined)");
   s->eager_fwd = false;
+  affine_note_backward(s, mueq);
   if (s->lazy.ev_pref) {
     HIP_TRY(hipStreamWaitEvent(s->stream, s->lazy.ev_pref, 0));
     s->pref_b = -1;

@@ -475,6 +475,47 @@ class BatchedRiccatiSolver:
         L, h = self._L, self._h
         return L.gar_hip_device_kkt_errors(h), L.gar_hip_device_kkt_stage_errors(h)
 
+    # ---- re-solve for new affine terms (gar_hip_backward_affine, csrc/gar_affine.hpp) ------------------------------
+    @property
+    def affine_doubles(self) -> int:
+        """doubles of one problem's affine vector: for t = 0..N: q_t r_t f_t, then g0 (the caller's dimensions)"""
+        return int(self._L.gar_hip_affine_doubles(self._h))
+
+    def pack_affine(self, problem: LqrProblem) -> np.ndarray:
+        """q, r, f of every knot and g0 of `problem` as one affine vector (gar_hip_affine_doubles)"""
+        parts = []
+        for k in problem.stages:
+            parts += [np.ravel(k.q), np.ravel(k.r), np.ravel(k.f)]
+        parts.append(np.ravel(problem.g0))
+        out = np.ascontiguousarray(np.concatenate(parts), dtype=np.float64)
+        if out.size != self.affine_doubles:
+            raise ValueError(f"affine vector of {out.size} entries, the solver's has {self.affine_doubles}")
+        return out
+
+    def upload_affine(self, arr: np.ndarray, b0: int = 0):
+        """gar_hip_upload_affine: arr holds a whole number of affine vectors, for problems b0 ...; only q, r, f, g0 of
+        the device knots change"""
+        arr = np.ascontiguousarray(arr, dtype=np.float64).reshape(-1)
+        n = self.affine_doubles
+        if n == 0 or arr.size % n != 0:
+            raise ValueError(f"{arr.size} entries are no whole number of affine vectors of {n}")
+        self._check(self._L.gar_hip_upload_affine(self._h, int(b0), arr.size // n, _ptr(arr)))
+
+    def upload_affine_device(self, ptr: int, b0: int = 0, nb: Optional[int] = None):
+        """gar_hip_upload_affine_device: `ptr` is the device address of nb affine vectors; enqueued, not waited for"""
+        nb = self.batch - b0 if nb is None else nb
+        self._check(self._L.gar_hip_upload_affine_device(self._h, int(b0), int(nb), C.c_void_p(ptr)))
+
+    def backward_affine(self) -> bool:
+        """gar_hip_backward_affine: the vector half of the last backward again, for the q, r, f, g0 the knots hold now"""
+        self._factors_cache = {}
+        self._check(self._L.gar_hip_backward_affine(self._h))
+        return True
+
+    def backward_affine_async(self):
+        self._factors_cache = {}
+        self._check(self._L.gar_hip_backward_affine_async(self._h))
+
     def slow_path_stages(self):
         """(stages of the last backward that left the register LDL^T because Rhat failed the first
         Bunch-Kaufman test, those of them where Bunch-Kaufman really pivoted), summed over the batch."""

@@ -339,6 +339,44 @@ int gar_hip_kkt_error(gar_hip_solver *s, double mueq, const double *theta_host, 
 const double *gar_hip_device_kkt_errors(gar_hip_solver *s);       /* [batch][3]      */
 const double *gar_hip_device_kkt_stage_errors(gar_hip_solver *s); /* [batch][N+1][4] */
 
+/* ---- re-solve for new affine terms from the stored factorisation (csrc/gar_affine.hpp; no reference counterpart) ------
+ * gar_hip_backward re-forms and re-factorises everything.  When only q, r, f of the knots and g0 have changed since the
+ * last backward -- tracking MPC over a batch, a refinement step whose right-hand side is the KKT residual, the adjoint
+ * of a differentiable LQ layer -- the VECTOR half of the recursion (riccati-kernel.hxx:209-277) is enough: it reads the
+ * stored fb = [K; Aff], Vxx', vx' and the knot's B, and rewrites ff, vx and kkt0.ff ONLY; fb, Vxx and the knots' matrix
+ * blocks keep their bits, and gar_hip_forward / the getters / gar_hip_kkt_error then serve the new problem unchanged.
+ * What the records lack, W = (R + B^T Vxx' B)^-1, is formed for every stage at once by the first re-solve after a
+ * backward and kept in a side buffer [batch][horizon + 1][nu^2] (allocated on first use, like the KKT buffers).
+ * The re-solved results equal a fresh gar_hip_backward of the same problem TO ROUNDING, not bitwise: an explicit inverse
+ * and the stored, rounded K and Aff are used (the tests bound the distance against the full solve's own).
+ *   gar_hip_affine_doubles        doubles of one problem's affine vector, the CALLER's dimensions:
+ *                                 for t = 0..N: q_t(nx) r_t(nu) f_t(nx2); then g0(nc0).  A terminal knot given with
+ *                                 nx2 = 0 contributes no f_t.
+ *   gar_hip_upload_affine         nb such vectors from the host into the knots of problems b0 ..: staged through the
+ *                                 pinned area, then scattered by a kernel through the stage descriptors (padding, ring);
+ *                                 nothing else of a record is touched.  Synchronous.
+ *   gar_hip_upload_affine_device  the same from a DEVICE pointer; enqueued, not waited for.
+ *   gar_hip_backward_affine       the re-solve: synchronous, returns like gar_hip_backward (GAR_HIP_ERR_FACTOR when the
+ *                                 last backward left failed problems); _async: enqueued, not waited for.  No mueq
+ *                                 argument: the initial stage uses the mueq of the backward being reused.
+ * State: needs a preceding gar_hip_backward* of this solver.  Any backward makes W stale (the next re-solve forms it
+ * again); an upload of matrix blocks -- gar_hip_upload_stage, gar_hip_upload_packed*, gar_hip_update_lq_subproblem_device,
+ * gar_hip_backward_blocks -- and gar_hip_cycle_append leave nothing to re-solve from: gar_hip_backward_affine then
+ * answers GAR_HIP_ERR_ARG, naming the call, until the next backward.  (gar_hip_set_init does not: kkt0 is factorised
+ * again by every re-solve.)  A device producer that writes matrix blocks in place through gar_hip_device_problems calls
+ * gar_hip_backward itself.  Problems whose status word is non-zero are left alone: records, status and
+ * gar_hip_num_failed stay as the backward left them.
+ * Everything is enqueued on the solver's stream (gar_hip_set_stream), behind the half streams of a pipelined sweep.
+ * Served: num_legs = 1 on one device, nc = nth = 0 on every knot, nx + nc0 <= 128 -- the wave<>, mfma<>, pair<> families
+ * and the any-dimension kernels, padded solvers, a terminal knot with nu = 0 and / or nx2 = 0 or with nu > 0, N = 0, any
+ * nc0 and G0.  Everything else -- constrained or parameterised knots, the serial fold, leg mode, the stage-dense solver,
+ * a multi-device handle -- answers GAR_HIP_ERR_UNSUPPORTED with nothing launched. */
+int64_t gar_hip_affine_doubles(const gar_hip_solver *s);
+int gar_hip_upload_affine(gar_hip_solver *s, int b0, int nb, const double *affine_host);
+int gar_hip_upload_affine_device(gar_hip_solver *s, int b0, int nb, const double *affine_dev);
+int gar_hip_backward_affine(gar_hip_solver *s);
+int gar_hip_backward_affine_async(gar_hip_solver *s);
+
 /* Diagnostics of the last backward (specialised kernel families; no reference counterpart): the
  * register LDL^T of Rhat is what Bunch-Kaufman does whenever its first test |a_kk| >= alpha*colmax
  * holds at every column (bunchkaufman.hpp:61); out[0] = stages (summed over the batch) where it did
