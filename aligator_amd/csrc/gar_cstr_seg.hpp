@@ -118,17 +118,12 @@ __global__ void __launch_bounds__(64, 1) gar_cseg_backward(MfmaParams P, int num
   }
   double *vflush;
   if (resumed && tstart < t_first) { // V' = Vxx, vx' = vx of knot tstart + 1: complete in its record
-    const double *rn = fac + (long long)(tstart + 1) * P.fac_rec;
-    for (int e = lane; e < NX * NX; e += 64) {
-      const int j = e / NX, i = e - j * NX;
-      V[i * PK + j] = rn[M::fVxx + gar_sym_index(1, NX, i, j)];
-    }
-    if (lane < NX)
-      vn[lane] = rn[M::fvx + lane];
+    sweep_value_from_record<NX, NU, NC, PK>(fac + (long long)(tstart + 1) * P.fac_rec, V, vn, lane);
     vflush = fac + (long long)(tstart + 1) * P.fac_rec + M::fVxx;
   } else if (last_leg) {
     // the true terminal knot (terminalSolve, nu = 0, :146-149, :175-178): Z = C / mu, zff = d / mu,
-    // Vxx = Q + C^T Z, vx = q + C^T zff
+    // Vxx = Q + C^T Z, vx = q + C^T zff -- sweep_terminal_knot (gar_mfma.hpp) written out: through the call the
+    // decoupled kernel takes 458 registers instead of 456 at (36, 12, 32)
     const double *rec = prob + P.in_offN;
     double *out = fac + P.fac_offN;
     for (int e = lane; e < NX * NX; e += 64) {
@@ -155,10 +150,7 @@ __global__ void __launch_bounds__(64, 1) gar_cseg_backward(MfmaParams P, int num
     }
     vflush = fac + P.fac_offN + M::tVxx;
   } else { // behind a leg end: no value function (see (1) above); the first stage's deferred flush goes to the dump slot
-    for (int e = lane; e < NX * PK; e += 64)
-      V[e] = 0.0;
-    if (lane < NX)
-      vn[lane] = 0.0;
+    sweep_zero_value<NX, PK, 64>(V, vn, lane);
     vflush = fac + CsegCfg<NX, NU, NC>::dump(N, leg);
   }
   wave_sync();

@@ -33,7 +33,6 @@ namespace gar {
 template <int NX, int NU>
 __global__ void __launch_bounds__(128, (NX + NU > 64) ? 1 : 2) gar_backward_pair_leg(MfmaParams P, int num_legs, int leg_begin) {
   using C = WaveCfg<NX, NU, 0>;
-  using M = MfmaCfg<NX, NU, 0>;
   constexpr int PK = C::PK;
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int leg = (int)blockIdx.x + leg_begin, b = (int)blockIdx.y;
@@ -48,67 +47,46 @@ __global__ void __launch_bounds__(128, (NX + NU > 64) ? 1 : 2) gar_backward_pair
   WaveLane<NX, NU, 0> L;
   wave_lane_init<NX, NU>(L, lane);
   int t_first;
-  if (last_leg) { // the true terminal knot (terminalSolve, nu = 0, :146-149, :175-178): Vxx = Q, vx = q
-    const double *rec = prob + P.in_offN;
-    double *out = fac + P.fac_offN;
-    for (int e = tid; e < NX * NX; e += 128) {
-      const int j = e / NX, i = e - j * NX;
-      const double v = (i >= j) ? rec[M::tQ + e] : rec[M::tQ + i * NX + j];
-      V[i * PK + j] = v;
-      out[M::tVxx + e] = v;
-    }
-    if (tid < NX) {
-      const double v = rec[M::tq + tid];
-      vn[tid] = v;
-      out[M::tvx + tid] = v;
-    }
+  if (last_leg) { // the true terminal knot
+    sweep_terminal_knot<NX, NU, 0, PK, 128, false>(prob + P.in_offN, fac + P.fac_offN, V, vn, tid, P.mueq);
     t_first = N - 1;
   } else { // behind a leg end: no value function (see (1) above)
-    for (int e = tid; e < NX * PK; e += 128)
-      V[e] = 0.0;
-    if (tid < NX)
-      vn[tid] = 0.0;
+    sweep_zero_value<NX, PK, 128>(V, vn, tid);
     t_first = t_end - 1;
   }
   __syncthreads();
   if (t_first < t_beg)
     return; // a leg made of the terminal knot alone
-  int failed = 0;
   const double *rec1 = prob + P.in_off0 + P.slot(t_first) * P.in_rec;
-#if GAR_PAIR_REFRESH_LANE
-  // (the lane offsets re-derived per stage, as in gar_backward_pair: the uneven first half of pair_stage needs the room)
+  int failed = 0;
+  // (one loop per wave, the lane offsets re-derived per stage: gar_backward_pair)
   if (wave == 0) {
     WaveStage<NX, NU> S;
     pair_load<NX, NU, 0>(rec1, L, S, lane);
     for (int t = t_first; t >= t_beg; --t) {
-      const int lane_t = lane + fence0(S.Fo[0][0][0]);
-      WaveLane<NX, NU, 0> Lt;
-      wave_lane_init<NX, NU>(Lt, lane_t);
-      pair_stage<NX, NU, 0>(P, sm, prob, fac, t, lane_t, Lt, S, failed);
+      if constexpr (GAR_PAIR_REFRESH_LANE) {
+        const int lane_t = lane + fence0(S.Fo[0][0][0]);
+        WaveLane<NX, NU, 0> Lt;
+        wave_lane_init<NX, NU>(Lt, lane_t);
+        pair_stage<NX, NU, 0>(P, sm, prob, fac, t, lane_t, Lt, S, failed);
+      } else {
+        pair_stage<NX, NU, 0>(P, sm, prob, fac, t, lane, L, S, failed);
+      }
     }
   } else {
     WaveStage<NX, NU> S;
     pair_load<NX, NU, 1>(rec1, L, S, lane);
     for (int t = t_first; t >= t_beg; --t) {
-      const int lane_t = lane + fence0(S.Fo[PairCfg<NX, NU>::SPLIT][0][0]);
-      WaveLane<NX, NU, 0> Lt;
-      wave_lane_init<NX, NU>(Lt, lane_t);
-      pair_stage<NX, NU, 1>(P, sm, prob, fac, t, lane_t, Lt, S, failed);
+      if constexpr (GAR_PAIR_REFRESH_LANE) {
+        const int lane_t = lane + fence0(S.Fo[PairCfg<NX, NU>::SPLIT][0][0]);
+        WaveLane<NX, NU, 0> Lt;
+        wave_lane_init<NX, NU>(Lt, lane_t);
+        pair_stage<NX, NU, 1>(P, sm, prob, fac, t, lane_t, Lt, S, failed);
+      } else {
+        pair_stage<NX, NU, 1>(P, sm, prob, fac, t, lane, L, S, failed);
+      }
     }
   }
-#else
-  if (wave == 0) {
-    WaveStage<NX, NU> S;
-    pair_load<NX, NU, 0>(rec1, L, S, lane);
-    for (int t = t_first; t >= t_beg; --t)
-      pair_stage<NX, NU, 0>(P, sm, prob, fac, t, lane, L, S, failed);
-  } else {
-    WaveStage<NX, NU> S;
-    pair_load<NX, NU, 1>(rec1, L, S, lane);
-    for (int t = t_first; t >= t_beg; --t)
-      pair_stage<NX, NU, 1>(P, sm, prob, fac, t, lane, L, S, failed);
-  }
-#endif
   if (failed && lane == 0)
     atomicOr(&P.status[b], failed);
 }

@@ -327,6 +327,63 @@ __device__ __forceinline__ void wave_flush_vxx(const double *V, double *dst, int
     VO::write(dst, q, lane, vbuf[q]);
 }
 
+// ---- where a backward sweep's V', vx' (LDS, pitch PK) come from: every specialised backward kernel starts with one of
+// these three, with NTHR threads (tid = 0 .. NTHR - 1) ----
+// The terminal knot (terminalSolve, nu = 0, :146-149, :175-178): Z = C / mu, zff = d / mu, Vxx = Q + C^T Z,
+// vx = q + C^T zff (nc = 0: Vxx = Q, vx = q), and its record `out`.  rec: the knot (its record keeps the full Q);
+// VXX_PACKED: the record keeps Vxx as the packed lower triangle (gar_layout.h) instead of the full block.
+template <int NX, int NU, int NC, int PK, int NTHR, bool VXX_PACKED>
+__device__ __forceinline__ void sweep_terminal_knot(const double *rec, double *out, double *V, double *vn, int tid,
+                                                    double mueq) {
+  using M = MfmaCfg<NX, NU, NC>;
+  for (int e = tid; e < NX * NX; e += NTHR) {
+    const int j = e / NX, i = e - j * NX; // column-major element (i, j)
+    double v = (i >= j) ? rec[M::tQ + e] : rec[M::tQ + i * NX + j];
+    for (int k = 0; k < NC; ++k) // (C^T Z)(i, j), Z = C / mu
+      v = __builtin_fma(rec[M::tC + i * NC + k], rec[M::tC + j * NC + k] / mueq, v);
+    V[i * PK + j] = v; // symmetrised from lower, as the consumer stage does (:216)
+    if (!VXX_PACKED)
+      out[M::tVxx + e] = v;
+    else if (i >= j)
+      out[M::tVxx + gar_sym_index(1, NX, i, j)] = v;
+  }
+  if (tid < NX) {
+    double v = rec[M::tq + tid];
+    for (int k = 0; k < NC; ++k)
+      v = __builtin_fma(rec[M::tC + tid * NC + k], rec[M::td + k] / mueq, v);
+    vn[tid] = v;
+    out[M::tvx + tid] = v;
+  }
+  if (NC > 0) { // ff = [zff; 0], fb = [Z; 0] (row-major: the terminal record keeps the generic layout)
+    for (int e = tid; e < NC + NX; e += NTHR)
+      out[e] = e < NC ? rec[M::td + e] / mueq : 0.0;
+    for (int e = tid; e < (NC + NX) * NX; e += NTHR) {
+      const int i = e / NX, j = e - i * NX;
+      out[(NC + NX) + e] = i < NC ? rec[M::tC + j * NC + i] / mueq : 0.0;
+    }
+  }
+}
+// A chain kernel that resumes (gar_backward_wave_body): V' = Vxx, vx' = vx of the knot above, complete in its record rn
+// (one wave; the one-wave serial families keep Vxx as the packed lower triangle)
+template <int NX, int NU, int NC, int PK>
+__device__ __forceinline__ void sweep_value_from_record(const double *rn, double *V, double *vn, int lane) {
+  using M = MfmaCfg<NX, NU, NC>;
+  for (int e = lane; e < NX * NX; e += 64) {
+    const int j = e / NX, i = e - j * NX;
+    V[i * PK + j] = rn[M::fVxx + gar_sym_index(!M::WIDE, NX, i, j)];
+  }
+  if (lane < NX)
+    vn[lane] = rn[M::fvx + lane];
+}
+// Behind a leg end (gar_leg_seg.hpp (1)): no value function
+template <int NX, int PK, int NTHR>
+__device__ __forceinline__ void sweep_zero_value(double *V, double *vn, int tid) {
+  for (int e = tid; e < NX * PK; e += NTHR)
+    V[e] = 0.0;
+  if (tid < NX)
+    vn[tid] = 0.0;
+}
+
 // (launch bounds: the kernel only ever runs with at most one workgroup per CU -- the library binds it while
 // batch <= #CUs --, so it could take the registers two resident workgroups share; measured: (256, 1) = 304 registers, no
 // scratch: 1.621 against 1.556 ms at batch 256, 1.494 against 1.528 at batch 1 -- kept at (256, 2) for the reporting point;
@@ -353,22 +410,8 @@ __global__ void __launch_bounds__(256, GAR_MFMA_MIN_BLOCKS) gar_backward_mfma(Mf
   if (tracing && t == (N >> 1))                                                \
     P.trace[wave * 16 + (id)] = (long long)clock64();
 
-  // ---- terminal knot (terminalSolve, nu = 0, nc = 0, :175-178): Vxx = Q, vx = q
   {
-    const double *rec = prob + P.in_offN;
-    double *out = fac + P.fac_offN;
-    for (int e = tid; e < NX * NX; e += 256) {
-      const int j = e / NX, i = e - j * NX; // column-major element (i, j)
-      const double v = (i >= j) ? rec[C::tQ + e] : rec[C::tQ + i * NX + j];
-      V[i * PK + j] = v; // symmetrised from lower, as the consumer stage does (:216)
-      if (i >= j)
-        out[C::tVxx + gar_sym_index(1, NX, i, j)] = v; // (packed lower triangle: gar_layout.h)
-    }
-    for (int e = tid; e < NX; e += 256) {
-      const double v = rec[C::tq + e];
-      vn[e] = v;
-      out[C::tvx + e] = v;
-    }
+    sweep_terminal_knot<NX, NU, 0, PK, 256, true>(prob + P.in_offN, fac + P.fac_offN, V, vn, tid, P.mueq);
     if (N >= 1) { // prologue: knot N-1 -> Ft[(N-1)&1]
       const double *r1 = prob + P.in_off0 + P.slot(N - 1) * P.in_rec;
       double *Ft = sm + (((N - 1) & 1) ? C::oFt1 : C::oFt0);

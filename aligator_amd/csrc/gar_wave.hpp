@@ -1251,48 +1251,12 @@ __device__ __forceinline__ void gar_backward_wave_body(const MfmaParams &P, int 
     wave_load_b<NX, NU, WaveLane<NX, NU, NC>, QP>(prob + P.in_off0 + P.slot(tstart) * P.in_rec, L, S);
   }
 
-  // ---- terminal knot (terminalSolve, nu = 0, :146-149, :175-178): Z = C/mu, zff = d/mu,
-  // Vxx = Q + C^T Z, vx = q + C^T zff (nc = 0: Vxx = Q, vx = q)
-  if (BK_RESUME && tstart < N - 1) {
-    // V' = Vxx, vx' = vx of knot tstart+1: complete in its record (the first kernel's deferred flush of
-    // that Vxx runs at the start of the stage it then abandoned)
-    const double *rn = fac + P.slot(tstart + 1) * P.fac_rec;
-    for (int e = lane; e < NX * NX; e += 64) {
-      const int j = e / NX, i = e - j * NX;
-      V[i * PK + j] = rn[M::fVxx + gar_sym_index(!M::WIDE, NX, i, j)]; // (packed lower triangle: gar_layout.h)
-    }
-    if (lane < NX)
-      vn[lane] = rn[M::fvx + lane];
-  } else {
-    const double *rec = prob + P.in_offN;
-    double *out = fac + P.fac_offN;
-    for (int e = lane; e < NX * NX; e += 64) {
-      const int j = e / NX, i = e - j * NX; // column-major element (i, j)
-      double v = (i >= j) ? rec[M::tQ + e] : rec[M::tQ + i * NX + j];
-      for (int k = 0; k < NC; ++k) // (C^T Z)(i, j), Z = C / mu
-        v = __builtin_fma(rec[M::tC + i * NC + k], rec[M::tC + j * NC + k] / P.mueq, v);
-      V[i * PK + j] = v; // symmetrised from lower, as the consumer stage does (:216)
-      if (M::WIDE)
-        out[M::tVxx + e] = v;
-      else if (i >= j)
-        out[M::tVxx + gar_sym_index(1, NX, i, j)] = v; // (packed lower triangle: gar_layout.h)
-    }
-    if (lane < NX) {
-      double v = rec[M::tq + lane];
-      for (int k = 0; k < NC; ++k)
-        v = __builtin_fma(rec[M::tC + lane * NC + k], rec[M::td + k] / P.mueq, v);
-      vn[lane] = v;
-      out[M::tvx + lane] = v;
-    }
-    if (NC > 0) { // ff = [zff; 0], fb = [Z; 0] (row-major: the terminal record keeps the generic layout)
-      for (int e = lane; e < NC + NX; e += 64)
-        out[e] = e < NC ? rec[M::td + e] / P.mueq : 0.0;
-      for (int e = lane; e < (NC + NX) * NX; e += 64) {
-        const int i = e / NX, j = e - i * NX;
-        out[(NC + NX) + e] = i < NC ? rec[M::tC + j * NC + i] / P.mueq : 0.0;
-      }
-    }
-  }
+  // (knot tstart + 1's record is complete: the first kernel's deferred flush of that Vxx runs at the start of the stage
+  // it then abandoned)
+  if (BK_RESUME && tstart < N - 1)
+    sweep_value_from_record<NX, NU, NC, PK>(fac + P.slot(tstart + 1) * P.fac_rec, V, vn, lane);
+  else
+    sweep_terminal_knot<NX, NU, NC, PK, 64, !M::WIDE>(prob + P.in_offN, fac + P.fac_offN, V, vn, lane, P.mueq);
   wave_sync();
   int failed = 0;
   // gar_wave2.hpp: a stage leaves its Vxx in LDS and the NEXT stage copies it to HBM behind its

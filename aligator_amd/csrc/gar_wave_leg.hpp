@@ -42,11 +42,28 @@ struct LegParams {
   const int *skip;         // folded solvers (gar_fold.hpp): problems with skip[b] != 0 belong to the generic kernels
 };
 
+// The final leg of the wave-leg kernels, one wave: the plain recursion from the true terminal knot (term_out: its
+// record, which keeps the full Vxx in this family) down to knot t_beg
+template <int NX, int NU>
+__device__ __forceinline__ void wave_leg_final(const MfmaParams &P, double *sm, const double *prob, double *fac,
+                                               double *term_out, int t_beg, int lane, const WaveLane<NX, NU> &L,
+                                               WaveStage<NX, NU> &S, int &failed, const bool tracing) {
+  using C = WaveCfg<NX, NU>;
+  const int N = P.horizon;
+  if (N - 1 >= t_beg) {
+    wave_load_a<NX, NU>(prob + P.in_off0 + (long long)(N - 1) * P.in_rec, L, S);
+    wave_load_b<NX, NU>(prob + P.in_off0 + (long long)(N - 1) * P.in_rec, L, S);
+  }
+  sweep_terminal_knot<NX, NU, 0, C::PK, 64, false>(prob + P.in_offN, term_out, sm + C::oV, sm + C::oVn, lane, P.mueq);
+  wave_sync();
+  for (int t = N - 1; t >= t_beg; --t)
+    wave_stage<NX, NU, 0>(P, sm, prob, fac, t, lane, L, S, failed, tracing);
+}
+
 template <int NX, int NU>
 __global__ void __launch_bounds__(64, 1) gar_backward_wave_leg(LegParams Q) {
   using C = WaveCfg<NX, NU>;
   using M = MfmaCfg<NX, NU>;
-  constexpr int PK = C::PK;
   const int lane = (int)threadIdx.x & 63;
   const int leg = (int)blockIdx.x + Q.leg_begin;
   const int b = (int)blockIdx.y;
@@ -63,7 +80,6 @@ __global__ void __launch_bounds__(64, 1) gar_backward_wave_leg(LegParams Q) {
   P.fac_rec = last_leg ? (long long)(M::fvx + NX) : (long long)C::prec;
   P.fac_rec = (P.fac_rec + 1) & ~1ll;
   double *fac = P.fac + (long long)b * P.fac_stride + Q.meta[t_beg].fac_off - (long long)t_beg * P.fac_rec;
-  double *V = sm + C::oV, *vn = sm + C::oVn;
   // debug build (make trace, -DGAR_TRACE; scripts/trace_leg.py): cycle stamps of the second stage of leg 0
   // (wave_stage stamps stage horizon/2); compiled out otherwise -- the run-time test alone costs
   // 3 % of the leg sweep
@@ -79,30 +95,8 @@ __global__ void __launch_bounds__(64, 1) gar_backward_wave_leg(LegParams Q) {
   WaveStage<NX, NU> S;
   int failed = 0;
   if (last_leg) {
-    // ---- true terminal knot (terminalSolve, nu = 0, nc = 0, :175-178): Vxx = Q, vx = q
-    const int t1 = N - 1 >= t_beg ? N - 1 : t_beg;
-    if (N - 1 >= t_beg) {
-      wave_load_a<NX, NU>(prob + P.in_off0 + (long long)t1 * P.in_rec, L, S);
-      wave_load_b<NX, NU>(prob + P.in_off0 + (long long)t1 * P.in_rec, L, S);
-    }
-    {
-      const double *rec = prob + P.in_offN;
-      double *out = P.fac + (long long)b * P.fac_stride + Q.meta[N].fac_off;
-      for (int e = lane; e < NX * NX; e += 64) {
-        const int j = e / NX, i = e - j * NX;
-        const double v = (i >= j) ? rec[M::tQ + e] : rec[M::tQ + i * NX + j];
-        V[i * PK + j] = v;
-        out[M::tVxx + e] = v;
-      }
-      if (lane < NX) {
-        const double v = rec[M::tq + lane];
-        vn[lane] = v;
-        out[M::tvx + lane] = v;
-      }
-    }
-    wave_sync();
-    for (int t = N - 1; t >= t_beg; --t)
-      wave_stage<NX, NU, 0>(P, sm, prob, fac, t, lane, L, S, failed, tracing);
+    wave_leg_final<NX, NU>(P, sm, prob, fac, P.fac + (long long)b * P.fac_stride + Q.meta[N].fac_off, t_beg, lane, L, S,
+                           failed, tracing);
   } else {
     const int te = t_end - 1;
     wave_load_a<NX, NU>(prob + P.in_off0 + (long long)te * P.in_rec, L, S);
@@ -342,7 +336,6 @@ template <int NX, int NU>
 __global__ void __launch_bounds__(128, 1) gar_backward_wave_leg2(LegParams Q) {
   using C = WaveCfg<NX, NU>;
   using M = MfmaCfg<NX, NU>;
-  constexpr int PK = C::PK;
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const int leg = (int)blockIdx.x + Q.leg_begin;
   const int b = (int)blockIdx.y;
@@ -358,7 +351,6 @@ __global__ void __launch_bounds__(128, 1) gar_backward_wave_leg2(LegParams Q) {
   P.fac_rec = last_leg ? (long long)(M::fvx + NX) : (long long)C::prec;
   P.fac_rec = (P.fac_rec + 1) & ~1ll;
   double *fac = P.fac + (long long)b * P.fac_stride + Q.meta[t_beg].fac_off - (long long)t_beg * P.fac_rec;
-  double *V = sm + C::oV, *vn = sm + C::oVn;
   const bool tracing = false;
   WaveLane<NX, NU> L;
   wave_lane_init<NX, NU>(L, lane);
@@ -367,29 +359,8 @@ __global__ void __launch_bounds__(128, 1) gar_backward_wave_leg2(LegParams Q) {
   if (last_leg) { // the plain recursion: one wave
     if (wave != 0)
       return;
-    const int t1 = N - 1 >= t_beg ? N - 1 : t_beg;
-    if (N - 1 >= t_beg) {
-      wave_load_a<NX, NU>(prob + P.in_off0 + (long long)t1 * P.in_rec, L, S);
-      wave_load_b<NX, NU>(prob + P.in_off0 + (long long)t1 * P.in_rec, L, S);
-    }
-    {
-      const double *rec = prob + P.in_offN;
-      double *out = P.fac + (long long)b * P.fac_stride + Q.meta[N].fac_off;
-      for (int e = lane; e < NX * NX; e += 64) {
-        const int j = e / NX, i = e - j * NX;
-        const double v = (i >= j) ? rec[M::tQ + e] : rec[M::tQ + i * NX + j];
-        V[i * PK + j] = v;
-        out[M::tVxx + e] = v;
-      }
-      if (lane < NX) {
-        const double v = rec[M::tq + lane];
-        vn[lane] = v;
-        out[M::tvx + lane] = v;
-      }
-    }
-    wave_sync();
-    for (int t = N - 1; t >= t_beg; --t)
-      wave_stage<NX, NU, 0>(P, sm, prob, fac, t, lane, L, S, failed, tracing);
+    wave_leg_final<NX, NU>(P, sm, prob, fac, P.fac + (long long)b * P.fac_stride + Q.meta[N].fac_off, t_beg, lane, L, S,
+                           failed, tracing);
   } else {
     const int te = t_end - 1;
     if (wave == 0) {

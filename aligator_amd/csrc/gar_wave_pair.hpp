@@ -569,64 +569,41 @@ __global__ void __launch_bounds__(128, (NX + NU > 64) ? 1 : 2) gar_backward_pair
   WaveLane<NX, NU, 0> L;
   wave_lane_init<NX, NU, 0, PKD>(L, lane);
   const double *recN1 = prob + P.in_off0 + P.slot(N - 1) * P.in_rec;
-  { // terminal knot (terminalSolve, nu = 0, :146-149, :175-178): Vxx = Q, vx = q (its record keeps the full Q)
-    const double *rec = prob + P.in_offN;
-    double *out = fac + P.fac_offN;
-    for (int e = tid; e < NX * NX; e += 128) {
-      const int j = e / NX, i = e - j * NX;
-      const double v = (i >= j) ? rec[M::tQ + e] : rec[M::tQ + i * NX + j];
-      V[i * PK + j] = v;
-      if (!PKD && M::WIDE)
-        out[M::tVxx + e] = v;
-      else if (i >= j)
-        out[M::tVxx + gar_sym_index(1, NX, i, j)] = v; // (packed lower triangle: gar_layout.h)
-    }
-    if (tid < NX) {
-      const double v = rec[M::tq + tid];
-      vn[tid] = v;
-      out[M::tvx + tid] = v;
-    }
-  }
+  sweep_terminal_knot<NX, NU, 0, PK, 128, PKD || !M::WIDE>(prob + P.in_offN, fac + P.fac_offN, V, vn, tid, P.mueq);
   __syncthreads();
   int failed = 0;
   // one loop per wave: each keeps only ITS tiles in registers across the stages (a common loop would
-  // carry the union of both waves' state through either path)
-#if GAR_PAIR_REFRESH_LANE
-  // (as in the coupled constrained stage, gar_wave.hpp: the lane offsets re-derived per stage
-  // from a lane index the compiler cannot prove loop-invariant, instead of ~100 values parked in accumulator registers
-  // and copied back at every use)
+  // carry the union of both waves' state through either path).
+  // GAR_PAIR_REFRESH_LANE: as in the constrained chain (chain_stage, gar_wave.hpp), the lane offsets are re-derived
+  // per stage from a lane index the compiler cannot prove loop-invariant, instead of ~100 values parked in accumulator
+  // registers and copied back at every use
   if (wave == 0) {
     WaveStage<NX, NU> S;
     pair_load<NX, NU, 0, PKD>(recN1, L, S, lane);
     for (int t = N - 1; t >= 0; --t) {
-      const int lane_t = lane + fence0(S.Fo[0][0][0]);
-      WaveLane<NX, NU, 0> Lt;
-      wave_lane_init<NX, NU, 0, PKD>(Lt, lane_t);
-      pair_stage<NX, NU, 0, PKD>(P, sm, prob, fac, t, lane_t, Lt, S, failed);
+      if constexpr (GAR_PAIR_REFRESH_LANE) {
+        const int lane_t = lane + fence0(S.Fo[0][0][0]);
+        WaveLane<NX, NU, 0> Lt;
+        wave_lane_init<NX, NU, 0, PKD>(Lt, lane_t);
+        pair_stage<NX, NU, 0, PKD>(P, sm, prob, fac, t, lane_t, Lt, S, failed);
+      } else {
+        pair_stage<NX, NU, 0, PKD>(P, sm, prob, fac, t, lane, L, S, failed);
+      }
     }
   } else {
     WaveStage<NX, NU> S;
     pair_load<NX, NU, 1, PKD>(recN1, L, S, lane);
     for (int t = N - 1; t >= 0; --t) {
-      const int lane_t = lane + fence0(S.Fo[PairCfg<NX, NU>::SPLIT][0][0]);
-      WaveLane<NX, NU, 0> Lt;
-      wave_lane_init<NX, NU, 0, PKD>(Lt, lane_t);
-      pair_stage<NX, NU, 1, PKD>(P, sm, prob, fac, t, lane_t, Lt, S, failed);
+      if constexpr (GAR_PAIR_REFRESH_LANE) {
+        const int lane_t = lane + fence0(S.Fo[PairCfg<NX, NU>::SPLIT][0][0]);
+        WaveLane<NX, NU, 0> Lt;
+        wave_lane_init<NX, NU, 0, PKD>(Lt, lane_t);
+        pair_stage<NX, NU, 1, PKD>(P, sm, prob, fac, t, lane_t, Lt, S, failed);
+      } else {
+        pair_stage<NX, NU, 1, PKD>(P, sm, prob, fac, t, lane, L, S, failed);
+      }
     }
   }
-#else
-  if (wave == 0) {
-    WaveStage<NX, NU> S;
-    pair_load<NX, NU, 0, PKD>(recN1, L, S, lane);
-    for (int t = N - 1; t >= 0; --t)
-      pair_stage<NX, NU, 0, PKD>(P, sm, prob, fac, t, lane, L, S, failed);
-  } else {
-    WaveStage<NX, NU> S;
-    pair_load<NX, NU, 1, PKD>(recN1, L, S, lane);
-    for (int t = N - 1; t >= 0; --t)
-      pair_stage<NX, NU, 1, PKD>(P, sm, prob, fac, t, lane, L, S, failed);
-  }
-#endif
   if (failed && lane == 0)
     atomicOr(&P.status[b], failed);
 }
