@@ -28,6 +28,8 @@
 //                         No register array, no scratch.
 // Problems whose status word is non-zero (a failed backward) are left alone by prepare and by the sweep; `ok[b]` tells
 // the initial stage which problems to take.
+// gar_refine_sweep is the sweep's second instance (backward_affine_wave<true>): q | r and f from a right-hand-side buffer
+// instead of the knot, ff and vx into a side buffer instead of the factor record, gated per problem (gar_refine.hpp).
 #pragma once
 #include "gar_device.hpp"
 #include "gar_kkt.hpp" // kkt_group_sum, GAR_KKT_GROUP: four lanes share a short row
@@ -49,7 +51,17 @@ struct AffineParams {
   int unx, unu, unc0; // scatter: the caller's (nx, nu) of a padded solver (unx = 0: not padded), the caller's nc0
   int qr_packed, vxx_packed, fb_t2;
   int nx_max; // the sweep's chain vector vx'
+  // gar_refine_sweep only (gar_refine.hpp; null / zero for the re-solve): q~ | r~, f~ of stage t are read from
+  // rhs[b][t * rhs_rec] (gar_kkt.hpp: refine_rhs_f) instead of the knot, and ff~ = [kff; yff], vx~ go to
+  // out[b][t * out_rec] (refine_out_vx) instead of the factor record; problems with gate[b] == 0 are left alone
+  const double *rhs;
+  double *out;
+  const int *gate;
+  long long rhs_stride, out_stride;
+  int rhs_rec, out_rec;
 };
+// offset of vx~ inside a stage's record of the correction: ff~ = kff (nu) | yff (nx2) | pad to even | vx~ (nx)
+__host__ __device__ inline int refine_out_vx(int nu, int nx2) { return (nu + nx2 + 1) & ~1; }
 
 // lds[k] = rec[a + k], k < n, by one wave.  rec is 16-byte aligned and &lds[0] has the parity of a: 16-byte loads from
 // the even offsets, eight in flight per lane before the first store, one double at an odd end.
@@ -188,8 +200,11 @@ struct AffStage {
   const gar_double2 *sV, *sFb, *sW, *sBf, *sQr;  // the first piece of each block in HBM
   int rV, rFb, rW, rBf, rQr;                     // LDS offset (doubles, even) of that piece
   int nV, nFb, nW, nBf, nQr;                     // pieces
-  double *frec;
+  double *frec; // where ff and vx go: the factor record (the refinement sweep: the stage's record of the correction)
   int ff, vx, nc;
+  int oF;                // f in LDS: behind B (the refinement sweep: a block of its own, from the right-hand side)
+  const gar_double2 *sF; // the refinement sweep's f~
+  int rF, nF;
 };
 __host__ __device__ inline int aff_span(int a, int n) { return n > 0 ? (((a & 1) + n + 1) & ~1) : 0; }
 __host__ __device__ inline int affine_sweep_lds_doubles(int nx_max, int nx, int nu, int nx2, int fb_t2, int vxx_packed) {
@@ -198,7 +213,7 @@ __host__ __device__ inline int affine_sweep_lds_doubles(int nx_max, int nx, int 
   return ((nx_max + 1) & ~1) + (nvv + 2) + (fb + 2) + (nu * nu + 2) + (nx2 * nu + nx2 + 2) + (nx + nu + 2) + (nx2 + 2) +
          2 * (nu + 2);
 }
-__device__ inline AffStage aff_describe(const AffineParams &P, int b, int t, int base) {
+template <bool REFINE> __device__ inline AffStage aff_describe(const AffineParams &P, int b, int t, int base) {
   AffStage s;
   const int N = P.horizon;
   const gar_stage_meta m = P.meta[t];
@@ -210,8 +225,14 @@ __device__ inline AffStage aff_describe(const AffineParams &P, int b, int t, int
   const gar_factor_offsets fn = gar_factor_layout(mn.nx, mn.nu, mn.nc, mn.nx2, mn.nth);
   const double *knot = P.prob + (long long)b * P.prob_stride + m.in_off;
   double *factors = P.fac + (long long)b * P.fac_stride;
-  s.frec = factors + m.fac_off;
-  s.ff = fo.ff, s.vx = fo.vx;
+  const double *frec = factors + m.fac_off; // fb is read from here
+  if constexpr (REFINE) {
+    s.frec = P.out + (long long)b * P.out_stride + (long long)t * P.out_rec;
+    s.ff = 0, s.vx = refine_out_vx(m.nu, m.nx2);
+  } else {
+    s.frec = factors + m.fac_off;
+    s.ff = fo.ff, s.vx = fo.vx;
+  }
   s.t2 = P.fb_t2 && !s.last;
   s.pitch = 2 * s.nr + 2;
   const int nvv = P.vxx_packed ? s.n2 * (s.n2 + 1) / 2 : s.n2 * s.n2;
@@ -225,11 +246,20 @@ __device__ inline AffStage aff_describe(const AffineParams &P, int b, int t, int
     return aff_span(a, n) / 2;
   };
   s.nV = block(factors + mn.fac_off, fn.Vxx, nvv, aff_span(fn.Vxx, nvv), s.sV, s.rV, s.oV);
-  s.nFb = block(s.frec, fo.fb, rows * s.nx, s.t2 ? ((s.nx + 1) / 2) * s.pitch : aff_span(fo.fb, rows * s.nx), s.sFb,
+  s.nFb = block(frec, fo.fb, rows * s.nx, s.t2 ? ((s.nx + 1) / 2) * s.pitch : aff_span(fo.fb, rows * s.nx), s.sFb,
                 s.rFb, s.oFb);
   s.nW = block(P.W + ((long long)b * (N + 1) + t) * P.w_rec, 0, s.nu * s.nu, aff_span(0, s.nu * s.nu), s.sW, s.rW, s.oW);
-  s.nBf = block(knot, o.B, s.n2 * s.nu + s.n2, aff_span(o.B, s.n2 * s.nu + s.n2), s.sBf, s.rBf, s.oBf); // B | f side by side
-  s.nQr = block(knot, o.q, s.nx + s.nu, aff_span(o.q, s.nx + s.nu), s.sQr, s.rQr, s.oQr);                 // q | r too
+  if constexpr (REFINE) { // B from the knot; f~ and q~ | r~ from the right-hand side (both start on an even double)
+    const double *rhs = P.rhs + (long long)b * P.rhs_stride + (long long)t * P.rhs_rec;
+    const int of = refine_rhs_f(s.nx, s.nu);
+    s.nBf = block(knot, o.B, s.n2 * s.nu, aff_span(o.B, s.n2 * s.nu), s.sBf, s.rBf, s.oBf);
+    s.nF = block(rhs, of, s.n2, aff_span(of, s.n2), s.sF, s.rF, s.oF);
+    s.nQr = block(rhs, 0, s.nx + s.nu, aff_span(0, s.nx + s.nu), s.sQr, s.rQr, s.oQr);
+  } else {
+    s.nBf = block(knot, o.B, s.n2 * s.nu + s.n2, aff_span(o.B, s.n2 * s.nu + s.n2), s.sBf, s.rBf, s.oBf); // B | f side by side
+    s.nQr = block(knot, o.q, s.nx + s.nu, aff_span(o.q, s.nx + s.nu), s.sQr, s.rQr, s.oQr);                 // q | r too
+    s.oF = s.oBf + s.n2 * s.nu, s.sF = nullptr, s.rF = s.nF = 0;
+  }
   s.oVplus = p, p += (s.n2 + 1) & ~1;
   s.oRhat = p, p += (s.nu + 1) & ~1;
   s.oKff = p;
@@ -243,18 +273,24 @@ __device__ __forceinline__ void aff_dma(const gar_double2 *src, int dst, int n, 
       wave_dma16(reinterpret_cast<const char *>(src + k0 + lane), d + 16 * k0);
 }
 
-__global__ void __launch_bounds__(64) gar_backward_affine(AffineParams P) {
+// REFINE: the same sweep on redirected operands (AffineParams::rhs, out, gate) -- gar_refine_sweep below
+template <bool REFINE> __device__ __forceinline__ void backward_affine_wave(const AffineParams &P) {
   const int b = (int)blockIdx.x, lane = (int)threadIdx.x, N = P.horizon;
-  const bool skip = P.status[b] != 0;
-  if (lane == 0)
-    P.ok[b] = skip ? 0 : 1;
-  if (skip)
-    return;
+  if constexpr (REFINE) {
+    if (P.gate[b] == 0) // (written by gar_kkt_reduce: failed problems, and those at or below the threshold)
+      return;
+  } else {
+    const bool skip = P.status[b] != 0;
+    if (lane == 0)
+      P.ok[b] = skip ? 0 : 1;
+    if (skip)
+      return;
+  }
   const int g = lane / GAR_KKT_GROUP, sub = lane % GAR_KKT_GROUP, ng = 64 / GAR_KKT_GROUP;
   double *vxn = gar_smem; // vx of stage t + 1: the chain
   const int base = (P.nx_max + 1) & ~1, pk = P.vxx_packed;
   for (int t = N; t >= 0; --t) {
-    const AffStage s = aff_describe(P, b, t, base);
+    const AffStage s = aff_describe<REFINE>(P, b, t, base);
     // ---- this stage's blocks: HBM -> LDS, every piece in flight before the one wait ----
     aff_dma(s.sV, s.rV, s.nV, lane);
     if (s.t2) { // pair block c of nr pieces to c * pitch
@@ -265,12 +301,14 @@ __global__ void __launch_bounds__(64) gar_backward_affine(AffineParams P) {
     }
     aff_dma(s.sW, s.rW, s.nW, lane);
     aff_dma(s.sBf, s.rBf, s.nBf, lane);
+    if constexpr (REFINE)
+      aff_dma(s.sF, s.rF, s.nF, lane);
     aff_dma(s.sQr, s.rQr, s.nQr, lane);
     GAR_WAIT_VMCNT(0);
     wave_sync();
     const int nx = s.nx, nu = s.nu, n2 = s.n2;
     const double *Vs = gar_smem + s.oV, *fbs = gar_smem + s.oFb, *Ws = gar_smem + s.oW, *Bs = gar_smem + s.oBf;
-    const double *fs = Bs + n2 * nu, *qs = gar_smem + s.oQr, *rs = qs + nx;
+    const double *fs = gar_smem + s.oF, *qs = gar_smem + s.oQr, *rs = qs + nx;
     double *vplus = gar_smem + s.oVplus, *rhat = gar_smem + s.oRhat, *kff = gar_smem + s.oKff;
     // ---- vplus = vx' + Vxx' f: element (i, j) of the lower triangle at F(min) + max ----
     for (int i = lane; i < n2; i += 64) {
@@ -338,5 +376,8 @@ __global__ void __launch_bounds__(64) gar_backward_affine(AffineParams P) {
     wave_sync();
   }
 }
+__global__ void __launch_bounds__(64) gar_backward_affine(AffineParams P) { backward_affine_wave<false>(P); }
+// the correction's vector sweep of a refinement step: affine_sweep_lds_doubles + 4 doubles of dynamic LDS
+__global__ void __launch_bounds__(64) gar_refine_sweep(AffineParams P) { backward_affine_wave<true>(P); }
 
 } // namespace gar

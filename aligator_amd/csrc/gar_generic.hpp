@@ -75,11 +75,13 @@ struct GenericParams {
 __device__ inline int initial_stage_ptr(const WG &w, const GenericParams &P, int b, int nx, int nth,
                                         const double *V0p, const double *v0, const double *Vxt0p,
                                         const double *Vtt0, const double *vt0, double *k0mat,
-                                        double *k0rhs, double *k0sub, int *piv0, int *ctrl0, int v0_packed = 0) {
+                                        double *k0rhs, double *k0sub, int *piv0, int *ctrl0, int v0_packed = 0,
+                                        const double *g0_from = nullptr, double *io_to = nullptr) {
+  // (g0_from, io_to: a refinement step's initial stage reads its g0 and writes its result elsewhere, gar_refine.hpp)
   const double *prob = P.prob + (long long)b * P.prob_stride;
   int failed = 0;
   const int nc0 = P.nc0, n0 = nx + nc0;
-  const double *G0 = prob + P.G0_off, *g0 = prob + P.g0_off;
+  const double *G0 = prob + P.G0_off, *g0 = g0_from ? g0_from : prob + P.g0_off;
   MatV K0 = colmajor(k0mat, n0);
   const int rld = 1 + nth;
   MatV R0 = rowmajor(k0rhs, rld); // [ff | fth]
@@ -104,7 +106,7 @@ __device__ inline int initial_stage_ptr(const WG &w, const GenericParams &P, int
   wg_bar(w);
   failed |= 2 * wg_bk_factor(w, n0, K0.p, n0, k0sub, piv0, ctrl0);
   wg_bk_solve(w, n0, K0.p, n0, k0sub, piv0, R0.p, rld, 1, rld);
-  double *io = P.init + (long long)b * P.init_stride;
+  double *io = io_to ? io_to : P.init + (long long)b * P.init_stride;
   for (int e = w.tid; e < n0; e += w.nthr)
     io[e] = R0(e, 0);
   for (int e = w.tid; e < n0 * nth; e += w.nthr) {
@@ -474,23 +476,24 @@ __global__ void __launch_bounds__(256) gar_initial_generic(GenericParams P) {
 __host__ __device__ inline int gar_initial_wave_lds_doubles(int n0, int nth) {
   return n0 * n0 + n0 * (1 + nth) + n0 + (n0 & 1) + (n0 + 16 + 1) / 2 * 1 + 8;
 }
-__global__ void __launch_bounds__(64) gar_initial_wave(GenericParams P) {
-  const WG w = wave_self();
+// problem b by the calling wave; -> the status bits of a failed factorisation.  vx0, g0, io null: stage 0's vx of the
+// factor record, the problem's g0, kkt0.ff of P.init (a refinement step passes its own three, gar_refine.hpp)
+__device__ inline int initial_wave_problem(const WG &w, const GenericParams &P, int b, const double *vx0 = nullptr,
+                                           const double *g0_from = nullptr, double *io_to = nullptr) {
   double *sm = gar_smem;
-  const int b = (int)blockIdx.x;
-  if (P.only && !P.only[b]) // (pipelined sweeps: only the problems the fused initial stage left behind)
-    return;
   const gar_stage_meta m0 = P.meta[0];
   const gar_factor_offsets fo = gar_factor_layout(m0.nx, m0.nu, m0.nc, m0.nx2, m0.nth);
   const double *rec = P.fac + (long long)b * P.fac_stride + m0.fac_off;
   const int n0 = m0.nx + P.nc0, nth = m0.nth;
+  if (!vx0)
+    vx0 = rec + fo.vx;
   // "x0 given" (G0 = +-I, nc0 = nx, no parameters): the closed form of the fused initial stage of
   // gar_backward_wave -- x0 = -s g0, lbd0 = -s (vx0 + Vxx0 x0) -- instead of the (2 nx)^2
   // Bunch-Kaufman factorisation (0.18 ms of a 2.1 ms single-problem sweep)
   if (P.init_closed && nth == 0 && P.nc0 == m0.nx && m0.nx <= 64) {
     const int nx = m0.nx;
     const double *prob = P.prob + (long long)b * P.prob_stride;
-    const double *G0 = prob + P.G0_off, *g0 = prob + P.g0_off;
+    const double *G0 = prob + P.G0_off, *g0 = g0_from ? g0_from : prob + P.g0_off;
     const double g00 = G0[0];
     bool ok = (g00 == 1.0 || g00 == -1.0);
     for (int e = w.lane; e < nx * nx; e += 64) {
@@ -504,22 +507,28 @@ __global__ void __launch_bounds__(64) gar_initial_wave(GenericParams P) {
       if (w.lane < nx)
         xs[w.lane] = x0;
       wave_sync();
-      double acc = rec[fo.vx + ix];
+      double acc = vx0[ix];
       for (int k = 0; k < nx; ++k)
         acc += rec[fo.Vxx + gar_sym_index(P.vxx_packed, nx, ix, k)] * xs[k]; // Vxx0 symmetric: row ix
-      double *io = P.init + (long long)b * P.init_stride;
+      double *io = io_to ? io_to : P.init + (long long)b * P.init_stride;
       if (w.lane < nx) {
         io[w.lane] = x0;
         io[nx + w.lane] = -g00 * acc;
       }
-      return;
+      return 0;
     }
   }
   double *k0mat = sm, *k0rhs = k0mat + n0 * n0, *k0sub = k0rhs + n0 * (1 + nth);
   int *piv0 = (int *)(k0sub + n0 + (n0 & 1));
-  const int failed = initial_stage_ptr(w, P, b, m0.nx, nth, rec + fo.Vxx, rec + fo.vx, rec + fo.Vxt,
-                                       rec + fo.Vtt, rec + fo.vt, k0mat, k0rhs, k0sub, piv0,
-                                       piv0 + n0, P.vxx_packed);
+  return initial_stage_ptr(w, P, b, m0.nx, nth, rec + fo.Vxx, vx0, rec + fo.Vxt, rec + fo.Vtt, rec + fo.vt, k0mat,
+                           k0rhs, k0sub, piv0, piv0 + n0, P.vxx_packed, g0_from, io_to);
+}
+__global__ void __launch_bounds__(64) gar_initial_wave(GenericParams P) {
+  const WG w = wave_self();
+  const int b = (int)blockIdx.x;
+  if (P.only && !P.only[b]) // (pipelined sweeps: only the problems the fused initial stage left behind)
+    return;
+  const int failed = initial_wave_problem(w, P, b);
   if (failed && w.tid == 0)
     atomicOr(&P.status[b], failed);
 }

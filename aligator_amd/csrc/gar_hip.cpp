@@ -35,6 +35,7 @@
 #include "gar_leg_seg.hpp"
 #include "gar_kkt.hpp"
 #include "gar_affine.hpp"
+#include "gar_refine.hpp"
 #include "gar_host.hpp"
 #include "gar_record_io.hpp"
 
@@ -1716,6 +1717,79 @@ int gar_hip_backward_affine(gar_hip_solver *s) {
   const int nf = gar_hip_num_failed(s);
   if (nf < 0)
     return fail(GAR_HIP_ERR_DEVICE, std::string("backward_affine: ") + hipGetErrorString(hipGetLastError()));
+  if (nf > 0)
+    return fail(GAR_HIP_ERR_FACTOR, "Failed stage LDL factorization (" + std::to_string(nf) + " problem(s))");
+  return GAR_HIP_OK;
+}
+
+// ---- iterative refinement from the stored factorisation (gar_refine.hpp; launches in gar_launch.hpp) -------------------
+namespace {
+// who is served and the state a step needs; then the buffers (first call) and everything a step must be ordered behind
+int refine_begin(gar_hip_solver *s, int steps, double threshold, const char *who) {
+  if (int rc = affine_check(s, who))
+    return rc;
+  const std::string w(who);
+  if (steps < 0 || threshold != threshold)
+    return fail(GAR_HIP_ERR_ARG, w + ": the step count must be >= 0 and the threshold not NaN");
+  if (!s->buf.aff_ready)
+    return fail(GAR_HIP_ERR_ARG, s->buf.aff_stale ? w + ": matrix blocks changed since the last backward (" + s->buf.aff_stale +
+                                                        "): call gar_hip_backward first"
+                                                  : w + ": no backward of this solver to refine from");
+  if (!s->buf.ref_fwd)
+    return fail(GAR_HIP_ERR_ARG, w + ": no forward since the last backward (there is no solution to refine)");
+  if (int rc = affine_buffers(s))
+    return rc;
+  if (int rc = kkt_buffers(s))
+    return rc;
+  if (int rc = refine_buffers(s))
+    return rc;
+  s->eager_fwd = false; // (the host copy gar_hip_backward_blocks left is the unrefined solution: a fetch copies again)
+  return commit(s);     // (a g0 staged through gar_hip_set_init)
+}
+} // namespace
+
+int gar_hip_refine_async(gar_hip_solver *s, int steps, double threshold) {
+  GAR_GUARD(s); // (a pipelined sweep: the solver's stream is ordered behind the half streams first)
+  if (int rc = refine_begin(s, steps, threshold, "gar_hip_refine_async"))
+    return rc;
+  RoctxRange range_("gar::refine");
+  for (int i = 0; i < steps; ++i) {
+    if (int rc = launch_refine_residual(s, threshold))
+      return rc;
+    if (int rc = launch_refine_correction(s))
+      return rc;
+  }
+  return launch_refine_residual(s, threshold); // the KKT buffers describe the solution that is in HBM
+}
+
+int gar_hip_refine(gar_hip_solver *s, int max_steps, double threshold, int32_t out2[2]) {
+  GAR_GUARD(s);
+  if (int rc = refine_begin(s, max_steps, threshold, "gar_hip_refine"))
+    return rc;
+  RoctxRange range_("gar::refine");
+  std::vector<int> gate((size_t)s->batch);
+  int steps = 0, remaining = 0;
+  for (;;) {
+    if (int rc = launch_refine_residual(s, threshold))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(gate.data(), s->buf.d_ref_gate.get(), sizeof(int) * gate.size(), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    remaining = 0;
+    for (int v : gate)
+      remaining += (v != 0);
+    if (remaining == 0 || steps == max_steps)
+      break;
+    if (int rc = launch_refine_correction(s))
+      return rc;
+    ++steps;
+  }
+  if (out2) {
+    out2[0] = steps;
+    out2[1] = remaining;
+  }
+  const int nf = gar_hip_num_failed(s);
+  if (nf < 0)
+    return fail(GAR_HIP_ERR_DEVICE, std::string("refine: ") + hipGetErrorString(hipGetLastError()));
   if (nf > 0)
     return fail(GAR_HIP_ERR_FACTOR, "Failed stage LDL factorization (" + std::to_string(nf) + " problem(s))");
   return GAR_HIP_OK;

@@ -260,6 +260,15 @@ struct LayoutState {
   bool aff_ready = false, aff_W_valid = false;
   double aff_mueq = 0.0;
   const char *aff_stale = nullptr;
+  // gar_hip_refine (gar_refine.hpp), all on the first call or none: the right-hand side (the residual vectors), the
+  // correction's ff~ / vx~, its initial stage's result, the gate words [batch]; the records' pitches and the three
+  // kernels' LDS (bytes).  ref_fwd: a roll-out has run since the last backward (there is a solution to refine)
+  DevBuf<double> d_ref_rhs, d_ref_out, d_ref_init;
+  DevBuf<int> d_ref_gate;
+  int ref_rhs_rec = 0, ref_out_rec = 0, ref_init_rec = 0;
+  long long ref_rhs_stride = 0, ref_out_stride = 0;
+  size_t ref_sweep_lds_bytes = 0, ref_roll_lds_bytes = 0, ref_init_lds_bytes = 0;
+  bool ref_fwd = false;
 };
 
 // Solver lifetime: the pipelined sweep's half streams and events (gar_hip_set_pipeline; the serial one-wave family,

@@ -51,7 +51,19 @@ struct KktParams {
   int horizon, nc0, nth0;
   int qr_packed; // knots t < horizon keep Q, R as packed lower triangles (gar_layout.h)
   double mueq;
+  // gar_hip_refine (gar_refine.hpp), all null / zero for every other caller: the residual VECTORS gx | gu, dyn of stage
+  // t go to rhs[b][t * rhs_rec] (refine_rhs_f(nx, nu) doubles between them), g0 + G0 x0 behind the last stage's; the
+  // reduction writes gate[b] = 1 where the problem is to be refined: status[b] == 0 and max(dynErr, dualErr) finite and
+  // above `threshold`
+  double *rhs;
+  int *gate;
+  const int *status;
+  long long rhs_stride;
+  int rhs_rec;
+  double threshold;
 };
+// offset of f~ inside a stage's right-hand-side record: q~ (nx) | r~ (nu) | pad to even | f~ (nx2)
+__host__ __device__ inline int refine_rhs_f(int nx, int nu) { return (nx + nu + 1) & ~1; }
 
 // LDS of gar_kkt_stage_residuals for one stage: the tile, the seven input vectors, the five residual vectors
 __host__ __device__ inline int kkt_lds_doubles(int nx, int nu, int nc, int nx2, int nth, int nc0) {
@@ -275,6 +287,19 @@ __global__ void __launch_bounds__(GAR_KKT_THREADS) gar_kkt_stage_residuals(KktPa
     }
   }
   __syncthreads();
+  if (P.rhs) { // the vectors themselves: the right-hand side of a refinement step (device dimensions)
+    double *out = P.rhs + (long long)b * P.rhs_stride + (long long)t * P.rhs_rec;
+    for (int k = tid; k < nx; k += nthr)
+      out[k] = gx[k];
+    for (int k = tid; k < nu; k += nthr)
+      out[nx + k] = gu[k];
+    if (!last)
+      for (int k = tid; k < nx2; k += nthr)
+        out[refine_rhs_f(nx, nu) + k] = dyn[k];
+    if (t == 0)
+      for (int k = tid; k < nc0; k += nthr)
+        P.rhs[(long long)b * P.rhs_stride + (long long)(N + 1) * P.rhs_rec + k] = ini[k];
+  }
   // the four infinity norms: norm q by wave q mod #waves alone (its 64 lanes stride over the vector, six shuffles fold them)
   const int lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
   for (int q = 0; q < 4; ++q) {
@@ -320,6 +345,10 @@ __global__ void __launch_bounds__(64) gar_kkt_reduce(KktParams P) {
     P.err[3 * (long long)b] = dynE;
     P.err[3 * (long long)b + 1] = cstE;
     P.err[3 * (long long)b + 2] = dualE;
+    if (P.gate) {
+      const double e = kkt_nanmax(dynE, dualE);
+      P.gate[b] = (P.status[b] == 0 && fabs(e) <= 1.7976931348623157e308 && !(e <= P.threshold)) ? 1 : 0;
+    }
   }
 }
 

@@ -16,6 +16,7 @@ inline void affine_note_backward(gar_hip_solver *s, double mueq) {
   s->buf.aff_W_valid = false;
   s->buf.aff_mueq = mueq;
   s->buf.aff_stale = nullptr;
+  s->buf.ref_fwd = false; // (gar_hip_refine: the solution in HBM is no longer this factorisation's)
 }
 inline void affine_invalidate(gar_hip_solver *s, const char *cause) {
   if (s->buf.aff_ready || s->buf.aff_stale) // (before the first backward there is nothing to make stale)
@@ -413,8 +414,7 @@ int forward_seg_or_generic(gar_hip_solver *s, const gar::GenericParams &P) {
   return GAR_HIP_OK;
 }
 
-int launch_forward(gar_hip_solver *s, const double *theta_dev) {
-  RoctxRange range_(s->num_legs > 1 ? "gar::parallel_forward" : "gar::forwardImpl");
+int forward_by_family(gar_hip_solver *s, const double *theta_dev) {
   if (s->leg_fwd_kernel)
     return forward_wave_legs(s);
   if (s->mfma_fwd_kernel)
@@ -427,6 +427,13 @@ int launch_forward(gar_hip_solver *s, const double *theta_dev) {
                      (size_t)s->lds.ftotal * sizeof(double), s->stream, P);
   HIP_TRY(hipGetLastError());
   return GAR_HIP_OK;
+}
+int launch_forward(gar_hip_solver *s, const double *theta_dev) {
+  RoctxRange range_(s->num_legs > 1 ? "gar::parallel_forward" : "gar::forwardImpl");
+  const int rc = forward_by_family(s, theta_dev);
+  if (rc == GAR_HIP_OK)
+    s->buf.ref_fwd = true; // (gar_hip_refine: there is a solution of this factorisation to refine)
+  return rc;
 }
 
 #include "gar_pipeline.hpp"
@@ -772,6 +779,93 @@ int launch_backward_affine(gar_hip_solver *s) {
   I.only = s->buf.d_aff_ok;
   hipLaunchKernelGGL(gar::gar_initial_wave, dim3((unsigned)s->batch), dim3(64),
                      (size_t)gar::gar_initial_wave_lds_doubles(s->n0, s->nth0) * sizeof(double), s->stream, I);
+  HIP_TRY(hipGetLastError());
+  return GAR_HIP_OK;
+}
+
+// ---- one refinement step from the stored factorisation (gar_refine.hpp): residual vectors, sweep, initial stage, roll-out --
+// the side buffers, on the first call after the layout was built (all or none), and the three kernels' LDS
+int refine_buffers(gar_hip_solver *s) {
+  if (s->buf.d_ref_gate)
+    return GAR_HIP_OK;
+  const int nx_max = s->buf.aff_nx_max; // (affine_buffers ran)
+  int rhs_rec = 2, out_rec = 2, lds = 0, rlds = 0;
+  for (const gar_stage_meta &m : s->meta) {
+    rhs_rec = std::max(rhs_rec, gar::refine_rhs_f(m.nx, m.nu) + ((m.nx2 + 1) & ~1));
+    out_rec = std::max(out_rec, gar::refine_out_vx(m.nu, m.nx2) + ((m.nx + 1) & ~1));
+    lds = std::max(lds, gar::affine_sweep_lds_doubles(nx_max, m.nx, m.nu, m.nx2, s->fb_t2, s->vxx_packed) + 4);
+    rlds = std::max(rlds, gar::refine_rollout_lds_doubles(nx_max, m.nx, m.nu, m.nx2, s->fb_t2, s->vxx_packed));
+  }
+  const int ilds = gar::gar_initial_wave_lds_doubles(s->n0, s->nth0);
+  if ((size_t)std::max(lds, std::max(rlds, ilds)) * sizeof(double) > kCuLdsBytes)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_refine: a stage's blocks need " +
+                                             std::to_string((size_t)std::max(lds, std::max(rlds, ilds)) * sizeof(double)) +
+                                             " B of LDS (> 160 KiB per CU)");
+  HIP_TRY(max_lds(gar::gar_refine_sweep, (size_t)lds));
+  HIP_TRY(max_lds(gar::gar_refine_rollout, (size_t)rlds));
+  HIP_TRY(max_lds(gar::gar_refine_initial, (size_t)ilds));
+  const int N = s->horizon, init_rec = std::max(2, (s->n0 + 1) & ~1);
+  const long long rhs_stride = (long long)(N + 1) * rhs_rec + ((s->nc0 + 1) & ~1) + 2;
+  const long long out_stride = (long long)(N + 1) * out_rec + 2; // (+ 2: the last stage names a record behind its own)
+  DevBuf<double> rhs, out, init;
+  DevBuf<int> gate;
+  HIP_TRY(rhs.zalloc((size_t)s->batch * (size_t)rhs_stride));
+  HIP_TRY(out.zalloc((size_t)s->batch * (size_t)out_stride));
+  HIP_TRY(init.zalloc((size_t)s->batch * (size_t)init_rec));
+  HIP_TRY(gate.zalloc((size_t)s->batch));
+  s->buf.d_ref_rhs = std::move(rhs);
+  s->buf.d_ref_out = std::move(out);
+  s->buf.d_ref_init = std::move(init);
+  s->buf.d_ref_gate = std::move(gate);
+  s->buf.ref_rhs_rec = rhs_rec, s->buf.ref_out_rec = out_rec, s->buf.ref_init_rec = init_rec;
+  s->buf.ref_rhs_stride = rhs_stride, s->buf.ref_out_stride = out_stride;
+  s->buf.ref_sweep_lds_bytes = (size_t)lds * sizeof(double);
+  s->buf.ref_roll_lds_bytes = (size_t)rlds * sizeof(double);
+  s->buf.ref_init_lds_bytes = (size_t)ilds * sizeof(double);
+  return GAR_HIP_OK;
+}
+
+// the KKT buffers of the solution in HBM (what gar_hip_kkt_error_async writes, at the mueq of the backward being reused),
+// the residual vectors into the right-hand side and the gate words of the next step
+int launch_refine_residual(gar_hip_solver *s, double threshold) {
+  gar::KktParams K = make_kkt_params(s, s->buf.aff_mueq, nullptr);
+  K.rhs = s->buf.d_ref_rhs;
+  K.gate = s->buf.d_ref_gate;
+  K.status = status_words(s);
+  K.rhs_stride = s->buf.ref_rhs_stride;
+  K.rhs_rec = s->buf.ref_rhs_rec;
+  K.threshold = threshold;
+  hipLaunchKernelGGL(gar::gar_kkt_stage_residuals, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)),
+                     dim3(GAR_KKT_THREADS), s->buf.kkt_lds_bytes, s->stream, K);
+  hipLaunchKernelGGL(gar::gar_kkt_reduce, dim3((unsigned)s->batch), dim3(64), 0, s->stream, K);
+  HIP_TRY(hipGetLastError());
+  return GAR_HIP_OK;
+}
+
+// the correction of the gated problems, added to the solution records
+int launch_refine_correction(gar_hip_solver *s) {
+  gar::AffineParams A = make_affine_params(s);
+  if (!s->buf.aff_W_valid) {
+    hipLaunchKernelGGL(gar::gar_affine_prepare, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)), dim3(64),
+                       s->buf.aff_prep_lds_bytes, s->stream, A);
+    HIP_TRY(hipGetLastError());
+    s->buf.aff_W_valid = true;
+  }
+  A.rhs = s->buf.d_ref_rhs;
+  A.out = s->buf.d_ref_out;
+  A.gate = s->buf.d_ref_gate;
+  A.rhs_stride = s->buf.ref_rhs_stride, A.out_stride = s->buf.ref_out_stride;
+  A.rhs_rec = s->buf.ref_rhs_rec, A.out_rec = s->buf.ref_out_rec;
+  gar::RefineParams R{};
+  R.G = make_params(s, s->buf.aff_mueq);
+  R.rhs = A.rhs, R.out = A.out, R.init = s->buf.d_ref_init, R.gate = A.gate;
+  R.rhs_stride = A.rhs_stride, R.out_stride = A.out_stride, R.init_rec = s->buf.ref_init_rec;
+  R.rhs_rec = A.rhs_rec, R.out_rec = A.out_rec;
+  R.fb_t2 = A.fb_t2, R.nx_max = A.nx_max;
+  const dim3 grid((unsigned)s->batch), wave(64);
+  hipLaunchKernelGGL(gar::gar_refine_sweep, grid, wave, s->buf.ref_sweep_lds_bytes, s->stream, A);
+  hipLaunchKernelGGL(gar::gar_refine_initial, grid, wave, s->buf.ref_init_lds_bytes, s->stream, R);
+  hipLaunchKernelGGL(gar::gar_refine_rollout, grid, wave, s->buf.ref_roll_lds_bytes, s->stream, R);
   HIP_TRY(hipGetLastError());
   return GAR_HIP_OK;
 }

@@ -135,6 +135,7 @@ int pipe_forward(gar_hip_solver *s) {
     if (s->timing)
       HIP_TRY(hipEventRecord(s->pipe.evT[h][3], st));
   }
+  s->buf.ref_fwd = true; // (gar_hip_refine: there is a solution of this factorisation to refine)
   return GAR_HIP_OK;
 }
 

@@ -516,6 +516,20 @@ class BatchedRiccatiSolver:
         self._factors_cache = {}
         self._check(self._L.gar_hip_backward_affine_async(self._h))
 
+    # ---- iterative refinement from the stored factorisation (gar_hip_refine, csrc/gar_refine.hpp) -------------------
+    def refine(self, max_steps: int = 1, threshold: float = -1.0):
+        """gar_hip_refine: up to max_steps refinement steps of the solution in HBM -- the KKT residual vectors as the
+        affine terms of a re-solve, the correction added to xs, us, lbdas -- for every problem whose max(dynErr, dualErr)
+        is finite and above `threshold` (< 0: every problem).  -> (steps run, problems still above the threshold).
+        Knots, factors and gains keep their bits; device_kkt_errors() then describe the refined solution."""
+        out = np.zeros(2, dtype=np.int32)
+        self._check(self._L.gar_hip_refine(self._h, int(max_steps), float(threshold), out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return int(out[0]), int(out[1])
+
+    def refine_async(self, steps: int = 1, threshold: float = -1.0):
+        """gar_hip_refine_async: exactly `steps` steps enqueued, not waited for; the threshold gates on the device"""
+        self._check(self._L.gar_hip_refine_async(self._h, int(steps), float(threshold)))
+
     def slow_path_stages(self):
         """(stages of the last backward that left the register LDL^T because Rhat failed the first
         Bunch-Kaufman test, those of them where Bunch-Kaufman really pivoted), summed over the batch."""

@@ -377,6 +377,39 @@ int gar_hip_upload_affine_device(gar_hip_solver *s, int b0, int nb, const double
 int gar_hip_backward_affine(gar_hip_solver *s);
 int gar_hip_backward_affine_async(gar_hip_solver *s);
 
+/* ---- iterative refinement of the resident batch from the stored factorisation (csrc/gar_refine.hpp) ------------------
+ * The Riccati recursion is not backward stable; the reference refines only the condensed system of its parallel solver
+ * (parallel-solver.hxx:187-199).  One step here, for every problem and entirely on the device:
+ *   rho   = the KKT residual VECTORS of the solution in HBM against the knots in HBM (gar_hip_kkt_error's terms):
+ *           q~ = gx, r~ = gu, f~ = A x + B u + f - x', g0~ = g0 + G0 x0
+ *   delta = the solution of the LQ problem with the SAME matrices and the affine terms rho, by the re-solve's vector
+ *           sweep from fb, Vxx and W, the initial stage on [vx~0; g0~], and a roll-out
+ *   xs, us, lbdas += delta
+ *   gar_hip_refine_async   exactly `steps` steps enqueued on the solver's stream (behind the half streams of a pipelined
+ *                          sweep), no host wait.  Before each step a problem is skipped ON THE DEVICE when its
+ *                          max(dynErr, dualErr) is <= threshold or not finite (a gate word per problem, written by the
+ *                          residual reduction); threshold < 0: never skipped.
+ *   gar_hip_refine         synchronous: after each evaluation the host reads how many problems are still above the
+ *                          threshold and stops at none, or after max_steps steps; out2 = {steps run, problems still above
+ *                          the threshold}.  Returns like gar_hip_backward_affine.
+ * Both end with one evaluation of the final solution: afterwards gar_hip_device_kkt_errors / _stage_errors describe the
+ * solution that is in HBM, at the mueq of the backward being reused -- what gar_hip_kkt_error_async would write.
+ * What keeps its bits: the knot records (the caller's q, r, f, g0 too), the whole factor records (ff, vx, kkt0.ff, fb,
+ * Vxx) and the status words -- gar_hip_get_gains and gar_hip_get_value answer as before the call.  Only the solution
+ * records and the KKT buffers change: the right-hand side and the correction's ff~, vx~ live in side buffers (allocated by
+ * the first call -- gar_hip_debug_alloc_count rises then and not again -- beside those of gar_hip_kkt_error and
+ * gar_hip_backward_affine).  The host copy of the solution gar_hip_backward_blocks left is dropped: the getters and
+ * gar_hip_fetch_results serve the refined solution.
+ * NO ROLLBACK: a step is kept whether or not it lowered the residual -- at the rounding floor of the residual (2 n eps S,
+ * DESIGN.md 5.3b) a step moves the triple by rounding only, up or down, as in the reference's condensed refinement.
+ * State (otherwise GAR_HIP_ERR_ARG naming the reason, nothing launched): a backward whose matrix blocks are still current
+ * (gar_hip_backward_affine's rules; W is formed if it is stale), a forward since that backward, steps >= 0, a threshold
+ * that is not NaN.  Problems whose status word is non-zero are left alone, solution included; gar_hip_refine then
+ * returns GAR_HIP_ERR_FACTOR.  Served: exactly who gar_hip_backward_affine serves; everyone else answers
+ * GAR_HIP_ERR_UNSUPPORTED with nothing launched and nothing touched. */
+int gar_hip_refine_async(gar_hip_solver *s, int steps, double threshold);
+int gar_hip_refine(gar_hip_solver *s, int max_steps, double threshold, int32_t out2[2] /* may be NULL */);
+
 /* Diagnostics of the last backward (specialised kernel families; no reference counterpart): the
  * register LDL^T of Rhat is what Bunch-Kaufman does whenever its first test |a_kk| >= alpha*colmax
  * holds at every column (bunchkaufman.hpp:61); out[0] = stages (summed over the batch) where it did
