@@ -14,7 +14,7 @@ int gar_hip_upload_stage(gar_hip_solver *s, int b, int t, const double *Q, const
   if (int rc = check_bt(s, b, t))
     return rc;
   GAR_MULTI(s, gar_hip_upload_stage(multi_owner(s, t), b, t, Q, S, R, q, r, A, B, f, C, D, d, Gth, Gx, Gu, Gv, gamma));
-  affine_invalidate(s, "gar_hip_upload_stage");
+  s->cur.matrices_changed("gar_hip_upload_stage");
   if (s->term_grown && t == s->horizon) // the caller's terminal A (0 x nx) and f are empty: zeros in the record
     A = f = s->term_zeros.data();
   const gar_stage_meta &u = caller_layout(s).meta[t], &m = s->meta[t];

@@ -163,7 +163,6 @@ struct gar_hip_solver : gar::HostLayout, gar::KernelBinding {
   std::unique_ptr<gar::HostLayout> flay;
   bool mu_divides = false; // some knot's solve divides by mueq outright (see gar_hip_backward_legs_async)
   bool any_nc = false;     // some knot carries constraints: a non-finite mueq is refused (ibid.)
-  double fold_mueq = 0.0;
   // leg mode
   int nxb = 0;
   int64_t tuple_doubles = 0, cscratch_doubles = 0;
@@ -174,20 +173,18 @@ struct gar_hip_solver : gar::HostLayout, gar::KernelBinding {
   bool cond_cr = false;      // ... and the J remaining blocks by block cyclic reduction, a workgroup per block and level
                              // (gar_condensed_cr.hpp; GAR_HIP_CONDENSED_CR=0: the one-workgroup chain, =<k>: from k legs on)
   int max_refinement = 5;        // parallel-solver.hpp:94
-  // run state (gar_host.hpp): what dies with the layout, and what is created on first use and dies with the solver
+  // run state (gar_host.hpp): what dies with the layout -- the buffers and what they hold right now -- and what is created
+  // on first use and dies with the solver
   gar::LayoutState buf;
+  gar::Current cur;
   gar::PipeState pipe;
   gar::LazyState lazy;
   Stream own_stream;            // created with the solver; `stream` is it or the caller's (gar_hip_set_stream)
   hipStream_t stream = nullptr;
   gar::LdsPlan lds{};
   gar::DensePlan dense_lds{};
-  int last_failed = 0;
   std::string lds_error;   // the generic kernels do not fit a CU's LDS (fatal unless a specialised family serves the shape)
   bool timing = false;         // gar_hip_set_timing (LazyState::ev)
-  int pref_b = -1;             // gar_hip_prefetch_gains: problem whose gains are in flight / in h_results (-1: none)
-  bool eager_fwd = false;      // d_sol and h_results hold the roll-out of the last sweep (theta = none)
-  bool pref_collapsed = false; // collapseFeedback ran since: stage 0's gains are fetched again
   int pipe_halves = 0;         // the pipelined sweep (PipeState), 0: off
   int pipe_requested = 0;      // what the caller last asked gar_hip_set_pipeline for (a rebuild re-validates it)
   // SolverProxDDP builds the terminal knot with nx2 = 0 (solvers/proxddp/workspace.hxx:54-55); nothing of the
@@ -663,7 +660,7 @@ gar::FoldParams make_fold_params(gar_hip_solver *s) {
   gar_get_work(s->horizon, s->leg_end - 1, s->num_legs, &dummy, &hi);
   F.t_lo = lo;
   F.t_hi = hi;
-  F.mueq = s->fold_mueq;
+  F.mueq = s->cur.mueq;
   F.qr_packed = s->qr_packed ? 1 : 0;
   F.lds = fold_lds_bytes(s) > 0 ? 1 : 0;
   return F;
@@ -685,33 +682,37 @@ gar::SerialFoldParams make_serial_fold_params(gar_hip_solver *s) {
 int ensure_expanded(gar_hip_solver *s) {
   if (!s->fold)
     return GAR_HIP_OK;
-  if (!s->buf.fold_expanded) {
+  if (!s->cur.expanded) {
     const dim3 grid((unsigned)(s->horizon + 1), (unsigned)s->batch);
     if (s->serial_fold)
       hipLaunchKernelGGL(gar::gar_expand_serial, grid, dim3(256), 0, s->stream, make_serial_fold_params(s));
     else
       hipLaunchKernelGGL(gar::gar_expand_constrained, grid, dim3(256), 0, s->stream, make_fold_params(s));
     HIP_TRY(hipGetLastError());
-    s->buf.fold_expanded = true;
+    s->cur.records_expanded();
   }
-  if (!s->buf.coupled_known) {
+  if (!s->cur.know_coupled) {
     s->buf.h_coupled.assign((size_t)s->batch, 0);
     HIP_TRY(hipMemcpyAsync(s->buf.h_coupled.data(), status_flags(s), sizeof(int) * (size_t)s->batch,
                            hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    s->buf.coupled_known = true;
+    s->cur.coupled_read();
   }
   return GAR_HIP_OK;
 }
 // fb / fth of problem b in the fbT2 device order?
 inline bool records_t2(const gar_hip_solver *s, int b) {
-  return s->fb_t2 && !(s->fold && s->buf.coupled_known && s->buf.h_coupled[(size_t)b] != 0);
+  return s->fb_t2 && !(s->fold && s->cur.coupled(s->buf.h_coupled, b));
 }
 
 // a kernel's opt-in to `doubles` of dynamic LDS (> 64 KiB needs it)
 template <class K> hipError_t max_lds(K kernel, size_t doubles) {
   return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(doubles * sizeof(double)));
 }
+
+// (defined beside prefetch_impl, which starts the read-back)
+enum { kBehindStream = 1, kBehindHost = 2 };
+int settle_gains_readback(gar_hip_solver *s, int behind);
 
 #include "gar_launch.hpp"
 
@@ -775,7 +776,6 @@ int allocate(gar_hip_solver *s) {
       HIP_TRY(max_lds(s->cseg.stage, s->cseg.stage_lds_doubles));
     }
   }
-  s->buf.fold_expanded = s->buf.coupled_known = false;
   const size_t staging = sizeof(double) * (size_t)s->prob_doubles * B;
   if (staging <= ((size_t)1 << 30)) {
     HIP_TRY(s->buf.h_prob.alloc((size_t)s->prob_doubles * B, hipHostMallocDefault));
@@ -1168,7 +1168,7 @@ int gar_hip_upload_packed(gar_hip_solver *s, int b0, int nb, const double *packe
     return GAR_HIP_OK;
   }
   GAR_MULTI(s, multi_upload_packed(s, b0, nb, packed)); // (each device its own range of the records)
-  affine_invalidate(s, "gar_hip_upload_packed");
+  s->cur.matrices_changed("gar_hip_upload_packed");
   const size_t bytes = sizeof(double) * (size_t)s->prob_doubles * nb;
   if (s->buf.staged) {
     std::memcpy(s->buf.h_prob + (int64_t)b0 * s->prob_doubles, packed, bytes);
@@ -1191,7 +1191,7 @@ int gar_hip_upload_packed_device(gar_hip_solver *s, int b0, int nb, const double
     return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_packed_device: bad argument");
   if (int rc = commit(s)) // staged host data first, then the device copy wins
     return rc;
-  affine_invalidate(s, "gar_hip_upload_packed_device");
+  s->cur.matrices_changed("gar_hip_upload_packed_device");
   HIP_TRY(hipMemcpyAsync(s->buf.d_prob + (int64_t)b0 * s->prob_doubles, packed_dev,
                          sizeof(double) * (size_t)s->prob_doubles * nb, hipMemcpyDeviceToDevice,
                          s->stream));
@@ -1255,12 +1255,9 @@ int gar_hip_backward_legs_async(gar_hip_solver *s, double mueq) {
     return fail(GAR_HIP_ERR_FACTOR, "Failed stage LDL factorization (mueq = " + std::to_string(mueq) +
                                         " on constrained knots)");
   GAR_MULTI(s, multi_backward_legs(s, mueq));
-  s->eager_fwd = false;
-  affine_note_backward(s, mueq);
-  if (s->lazy.ev_pref) { // a read-back of the previous sweep's gains may still be in flight on the second stream
-    HIP_TRY(hipStreamWaitEvent(s->stream, s->lazy.ev_pref, 0));
-    s->pref_b = -1;
-  }
+  s->cur.backward_enqueued(mueq);
+  if (int rc = settle_gains_readback(s, kBehindStream))
+    return rc;
   if (int rc = commit(s))
     return rc;
   HIP_TRY(hipMemsetAsync(status_words(s), 0, status_bytes((size_t)s->batch, s->fold), s->stream));
@@ -1315,6 +1312,25 @@ const char *gar_hip_get_option(const char *name) {
 }
 
 namespace {
+std::string failed_stages_text(int nf) { return "Failed stage LDL factorization (" + std::to_string(nf) + " problem(s))"; }
+// how a blocking entry point (`who`: its short name) ends: the host waits for the status words of the sweep it enqueued
+int failure_epilogue(gar_hip_solver *s, const char *who) {
+  const int nf = gar_hip_num_failed(s);
+  if (nf < 0)
+    return fail(GAR_HIP_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(hipGetLastError()));
+  return nf > 0 ? fail(GAR_HIP_ERR_FACTOR, failed_stages_text(nf)) : GAR_HIP_OK;
+}
+// two of the status counters (status_counters), from `first` on
+int read_counters(gar_hip_solver *s, int first, int64_t out[2]) {
+  if (!s || !out)
+    return fail(GAR_HIP_ERR_ARG, "bad argument");
+  int c[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(c, status_counters(s) + first, sizeof(c), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  out[0] = c[0];
+  out[1] = c[1];
+  return GAR_HIP_OK;
+}
 bool pipe_eligible(const gar_hip_solver *s) {
   return !(s->multi || s->world > 1 || s->num_legs != 1 || s->nth0 != 0 || s->batch < 2 || !s->wave_kernel || !s->lean_fwd_kernel ||
            !s->wave_half_kernel || s->wave_coupled_kernel || s->wave_block_threads != 64 || s->waves_per_block != 1 || !s->vxx_packed ||
@@ -1493,18 +1509,16 @@ int gar_hip_backward_blocks(gar_hip_solver *s, const double *const *blocks, cons
   int nf = 0;
   for (int b = 0; b < s->batch; ++b)
     nf += (s->lazy.h_status[b] != 0);
-  s->last_failed = nf;
   if (nf > 0) {
     // the roll-out, the solution's copy and the gains' read-back of the FAILED sweep are already enqueued: let them
     // finish and disarm the "already in flight" shortcuts, so that a later fetch does its own work (and nobody is
     // handed these gains as if the sweep had succeeded)
-    if (s->lazy.ev_pref)
-      HIP_TRY(hipEventSynchronize(s->lazy.ev_pref));
-    s->pref_b = -1;
-    s->eager_fwd = false;
-    return fail(GAR_HIP_ERR_FACTOR, "Failed stage LDL factorization (" + std::to_string(nf) + " problem(s))");
+    if (int rc = settle_gains_readback(s, kBehindHost))
+      return rc;
+    s->cur.solution_superseded();
+    return fail(GAR_HIP_ERR_FACTOR, failed_stages_text(nf));
   }
-  s->eager_fwd = true;
+  s->cur.host_solution_enqueued();
   return GAR_HIP_OK;
 }
 
@@ -1521,48 +1535,26 @@ int gar_hip_num_failed(gar_hip_solver *s) {
   int n = 0;
   for (int v : st)
     n += (v != 0);
-  s->last_failed = n;
   return n;
 }
 
 int gar_hip_slow_path_stages(gar_hip_solver *s, int64_t out[2]) {
   GAR_GUARD(s);
   GAR_MULTI(s, multi_counters(s, out, gar_hip_slow_path_stages));
-  if (!s || !out)
-    return fail(GAR_HIP_ERR_ARG, "bad argument");
-  int c[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(c, status_counters(s), sizeof(c), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  out[0] = c[0];
-  out[1] = c[1];
-  return GAR_HIP_OK;
+  return read_counters(s, 0, out);
 }
 
 int gar_hip_constrained_bk_stages(gar_hip_solver *s, int64_t out[2]) {
   GAR_GUARD(s);
   GAR_MULTI(s, multi_counters(s, out, gar_hip_constrained_bk_stages));
-  if (!s || !out)
-    return fail(GAR_HIP_ERR_ARG, "bad argument");
-  int c[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(c, status_counters(s) + 2, sizeof(c), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  out[0] = c[0];
-  out[1] = c[1];
-  return GAR_HIP_OK;
+  return read_counters(s, 2, out);
 }
 
 int gar_hip_backward(gar_hip_solver *s, double mueq) {
   GAR_GUARD(s);
   if (int rc = gar_hip_backward_async(s, mueq))
     return rc;
-  const int nf = gar_hip_num_failed(s);
-  if (nf < 0)
-    return fail(GAR_HIP_ERR_DEVICE, std::string("backward: ") +
-                                        hipGetErrorString(hipGetLastError()));
-  if (nf > 0)
-    return fail(GAR_HIP_ERR_FACTOR, "Failed stage LDL factorization (" + std::to_string(nf) +
-                                        " problem(s))");
-  return GAR_HIP_OK;
+  return failure_epilogue(s, "backward");
 }
 
 int gar_hip_forward_async(gar_hip_solver *s, const double *theta_device) {
@@ -1585,7 +1577,7 @@ int gar_hip_forward(gar_hip_solver *s, const double *theta) {
       return rc;
     return multi_sync(s);
   }
-  if (s->eager_fwd) { // enqueued behind the sweep by gar_hip_backward_blocks (no parameter: theta has no say)
+  if (s->cur.host_solution) { // enqueued behind the sweep by gar_hip_backward_blocks (no parameter: theta has no say)
     HIP_TRY(hipEventSynchronize(s->lazy.ev_sol));
     return GAR_HIP_OK;
   }
@@ -1701,10 +1693,9 @@ int gar_hip_backward_affine_async(gar_hip_solver *s) {
   GAR_GUARD(s); // (a pipelined sweep: the solver's stream is ordered behind the half streams first)
   if (int rc = affine_check(s, "gar_hip_backward_affine"))
     return rc;
-  if (!s->buf.aff_ready)
-    return fail(GAR_HIP_ERR_ARG, s->buf.aff_stale ? std::string("gar_hip_backward_affine: matrix blocks changed since the last backward (") +
-                                                        s->buf.aff_stale + "): call gar_hip_backward first"
-                                                  : std::string("gar_hip_backward_affine: no backward of this solver to re-solve from"));
+  const std::string refusal = s->cur.no_factors("gar_hip_backward_affine", "re-solve");
+  if (!refusal.empty())
+    return fail(GAR_HIP_ERR_ARG, refusal);
   if (int rc = affine_buffers(s))
     return rc;
   return launch_backward_affine(s);
@@ -1714,12 +1705,7 @@ int gar_hip_backward_affine(gar_hip_solver *s) {
   GAR_GUARD(s);
   if (int rc = gar_hip_backward_affine_async(s))
     return rc;
-  const int nf = gar_hip_num_failed(s);
-  if (nf < 0)
-    return fail(GAR_HIP_ERR_DEVICE, std::string("backward_affine: ") + hipGetErrorString(hipGetLastError()));
-  if (nf > 0)
-    return fail(GAR_HIP_ERR_FACTOR, "Failed stage LDL factorization (" + std::to_string(nf) + " problem(s))");
-  return GAR_HIP_OK;
+  return failure_epilogue(s, "backward_affine");
 }
 
 // ---- iterative refinement from the stored factorisation (gar_refine.hpp; launches in gar_launch.hpp) -------------------
@@ -1731,11 +1717,10 @@ int refine_begin(gar_hip_solver *s, int steps, double threshold, const char *who
   const std::string w(who);
   if (steps < 0 || threshold != threshold)
     return fail(GAR_HIP_ERR_ARG, w + ": the step count must be >= 0 and the threshold not NaN");
-  if (!s->buf.aff_ready)
-    return fail(GAR_HIP_ERR_ARG, s->buf.aff_stale ? w + ": matrix blocks changed since the last backward (" + s->buf.aff_stale +
-                                                        "): call gar_hip_backward first"
-                                                  : w + ": no backward of this solver to refine from");
-  if (!s->buf.ref_fwd)
+  const std::string refusal = s->cur.no_factors(w, "refine");
+  if (!refusal.empty())
+    return fail(GAR_HIP_ERR_ARG, refusal);
+  if (!s->cur.rolled_out)
     return fail(GAR_HIP_ERR_ARG, w + ": no forward since the last backward (there is no solution to refine)");
   if (int rc = affine_buffers(s))
     return rc;
@@ -1743,7 +1728,7 @@ int refine_begin(gar_hip_solver *s, int steps, double threshold, const char *who
     return rc;
   if (int rc = refine_buffers(s))
     return rc;
-  s->eager_fwd = false; // (the host copy gar_hip_backward_blocks left is the unrefined solution: a fetch copies again)
+  s->cur.solution_superseded(); // (the host copy gar_hip_backward_blocks left is the unrefined solution)
   return commit(s);     // (a g0 staged through gar_hip_set_init)
 }
 } // namespace
@@ -1787,12 +1772,7 @@ int gar_hip_refine(gar_hip_solver *s, int max_steps, double threshold, int32_t o
     out2[0] = steps;
     out2[1] = remaining;
   }
-  const int nf = gar_hip_num_failed(s);
-  if (nf < 0)
-    return fail(GAR_HIP_ERR_DEVICE, std::string("refine: ") + hipGetErrorString(hipGetLastError()));
-  if (nf > 0)
-    return fail(GAR_HIP_ERR_FACTOR, "Failed stage LDL factorization (" + std::to_string(nf) + " problem(s))");
-  return GAR_HIP_OK;
+  return failure_epilogue(s, "refine");
 }
 
 int gar_hip_get_status(gar_hip_solver *s, int32_t *out) {
@@ -1897,24 +1877,23 @@ static int fetch_results_impl(gar_hip_solver *s, int b, int what, int t_lo, int 
     s->buf.d_gains = std::move(dg);
     s->buf.d_gain_off = std::move(dgo);
   }
-  if ((what & 2) && s->pref_b == b && !gains_base && t_lo == 0 && t_hi == s->horizon + 1) {
+  if ((what & 2) && s->cur.gains_on_their_way(b) && !gains_base && t_lo == 0 && t_hi == s->horizon + 1) {
     // the gains are already on their way (gar_hip_prefetch_gains): wait for them; what collapseFeedback changed
     // since -- stage 0 -- comes again
-    HIP_TRY(hipEventSynchronize(s->lazy.ev_pref));
-    s->pref_b = -1;
-    if (!s->pref_collapsed)
+    if (int rc = settle_gains_readback(s, kBehindHost))
+      return rc;
+    if (!s->cur.gains_collapsed)
       what &= ~2;
     else
       t_hi = 1;
   }
   if ((what & 2) && t_hi > t_lo) { // device-side gather (fbT2 -> row-major, dummy rows / columns dropped), then ONE device-to-host copy
-    if (s->pref_b >= 0 && s->lazy.ev_pref) {
-      // a read-back started by gar_hip_prefetch_gains (of another problem, or of this one over another range) may
-      // still be writing d_gains / h_results on the second stream: this gather and copy reuse both
-      HIP_TRY(hipStreamWaitEvent(s->stream, s->lazy.ev_pref, 0));
-      HIP_TRY(hipEventSynchronize(s->lazy.ev_pref)); // (h_results is host memory: the caller may read it right after)
-      s->pref_b = -1;
-    }
+    // a read-back started by gar_hip_prefetch_gains (of another problem, or of this one over another range) may
+    // still be writing d_gains / h_results on the second stream: this gather and copy reuse both (h_results is host
+    // memory: the caller may read it right after)
+    if (s->cur.gains_in_flight())
+      if (int rc = settle_gains_readback(s, kBehindStream | kBehindHost))
+        return rc;
     if (int rc = ensure_expanded(s))
       return rc;
     const bool t2 = records_t2(s, b);
@@ -1937,7 +1916,7 @@ static int fetch_results_impl(gar_hip_solver *s, int b, int what, int t_lo, int 
                                sizeof(double) * (size_t)(b1 - b0), hipMemcpyDeviceToHost, s->stream));
     }
   }
-  const bool sol_there = (what & 1) && s->eager_fwd && b == 0; // copied behind the eager roll-out (gar_hip_backward_blocks)
+  const bool sol_there = (what & 1) && s->cur.host_solution && b == 0; // copied behind the eager roll-out (gar_hip_backward_blocks)
   if ((what & 1) && !sol_there)
     HIP_TRY(hipMemcpyAsync(s->buf.h_results + (s->padded ? nsol + ngain : 0), s->buf.d_sol + (int64_t)b * s->sol_doubles,
                            sizeof(double) * (size_t)s->sol_doubles, hipMemcpyDeviceToHost, s->stream));
@@ -1951,6 +1930,23 @@ static int fetch_results_impl(gar_hip_solver *s, int b, int what, int t_lo, int 
     strip_solution_rec(s, s->buf.h_results + nsol + ngain, s->buf.h_results);
   return GAR_HIP_OK;
 }
+
+// A read-back of the gains started by prefetch_impl may still be in flight on the second stream: the solver's stream
+// (kBehindStream: it is about to rewrite the factor records or d_gains), the host (kBehindHost: it is about to read or
+// release h_results) or both are ordered behind it, and the record learns that none is in flight.  The one place that
+// waits on LazyState::ev_pref.
+namespace {
+int settle_gains_readback(gar_hip_solver *s, int behind) {
+  if (s->lazy.ev_pref) {
+    if (behind & kBehindStream)
+      HIP_TRY(hipStreamWaitEvent(s->stream, s->lazy.ev_pref, 0));
+    if (behind & kBehindHost)
+      HIP_TRY(hipEventSynchronize(s->lazy.ev_pref));
+  }
+  s->cur.gains_settled();
+  return GAR_HIP_OK;
+}
+} // namespace
 
 // every stage's gains of problem b: gather + ONE device-to-host copy on the second stream, behind what the main
 // stream holds now
@@ -1978,8 +1974,7 @@ static int prefetch_impl(gar_hip_solver *s, int b) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(s->buf.h_results + nsol, s->buf.d_gains, sizeof(double) * ngain, hipMemcpyDeviceToHost, s->lazy.aux_stream));
   HIP_TRY(hipEventRecord(s->lazy.ev_pref, s->lazy.aux_stream));
-  s->pref_b = b;
-  s->pref_collapsed = false;
+  s->cur.gains_prefetched(b);
   return GAR_HIP_OK;
 }
 
@@ -1998,7 +1993,7 @@ int gar_hip_prefetch_gains(gar_hip_solver *s, int b) {
   // (multi-device and folded solvers: the ordinary fetch does the work -- their read-back has host-side steps)
   if (s->multi || s->fold)
     return GAR_HIP_OK;
-  if (s->eager_fwd && s->pref_b == b && !s->pref_collapsed)
+  if (s->cur.host_solution && s->cur.gains_on_their_way(b) && !s->cur.gains_collapsed)
     return GAR_HIP_OK; // gar_hip_backward_blocks started it already
   return prefetch_impl(s, b);
 }
@@ -2069,7 +2064,7 @@ int gar_hip_update_lq_subproblem_device(gar_hip_solver *s, const double *deriv_d
   GAR_MULTI(s, fail(GAR_HIP_ERR_UNSUPPORTED, "device-resident LQ assembly on a multi-device solver: one derivative buffer per device would be needed"));
   if (int rc = commit(s)) // pending host staging first; later host writes flush only their own ranges
     return rc;
-  affine_invalidate(s, "gar_hip_update_lq_subproblem_device");
+  s->cur.matrices_changed("gar_hip_update_lq_subproblem_device");
   const gar::HostLayout &u = caller_layout(s); // the layout of the derivative buffer: the caller's dimensions
   if (!s->buf.d_deriv_off) {
     HIP_TRY(s->buf.d_deriv_off.alloc(u.deriv_off.size()));
@@ -2189,8 +2184,7 @@ int gar_hip_collapse_feedback(gar_hip_solver *s) {
   if (!s)
     return fail(GAR_HIP_ERR_ARG, "null solver");
   GAR_MULTI(s, gar_hip_collapse_feedback(s->multi->subs[0])); // stage 0 lives on the first device
-  s->pref_collapsed = true;
-  s->eager_fwd = false; // a roll-out after this call is a new one
+  s->cur.feedback_collapsed();
   if (s->num_legs < 2 || s->leg_begin != 0)
     return GAR_HIP_OK; // no-op except Parallel (riccati-base.hpp:33)
   if (s->fold) { // the wave-leg family's own records (then re-expanded on request); flagged problems: generic records
@@ -2199,7 +2193,7 @@ int gar_hip_collapse_feedback(gar_hip_solver *s) {
                        (long long)s->flay->fac_doubles, s->batch, flags, 0);
     hipLaunchKernelGGL(gar::gar_collapse_feedback, dim3((unsigned)s->batch), dim3(256), 0, s->stream, s->buf.d_meta.get(), s->buf.d_fac.get(),
                        (long long)s->fac_doubles, s->batch, flags, 1);
-    s->buf.fold_expanded = false;
+    s->cur.expansion_outdated();
   } else {
     hipLaunchKernelGGL(s->leg_collapse_kernel ? s->leg_collapse_kernel : gar::gar_collapse_feedback,
                        dim3((unsigned)s->batch), dim3(256), 0, s->stream, s->buf.d_meta.get(), s->buf.d_fac.get(),
@@ -2214,11 +2208,10 @@ int gar_hip_cycle_append(gar_hip_solver *s, const int32_t d[5]) {
   if (!s || !d)
     return fail(GAR_HIP_ERR_ARG, "bad argument");
   GAR_MULTI(s, multi_cycle_append(s, d));
-  if (s->lazy.ev_pref)
-    HIP_TRY(hipEventSynchronize(s->lazy.ev_pref));
-  s->pref_b = -1;
-  s->eager_fwd = false;
-  affine_invalidate(s, "gar_hip_cycle_append");
+  if (int rc = settle_gains_readback(s, kBehindHost))
+    return rc;
+  s->cur.solution_superseded();
+  s->cur.matrices_changed("gar_hip_cycle_append");
   const int N = s->horizon;
   if (N < 1)
     return GAR_HIP_OK;
@@ -2264,7 +2257,7 @@ int gar_hip_cycle_append(gar_hip_solver *s, const int32_t d[5]) {
                              s->stream));
       HIP_TRY(hipMemset2DAsync(s->buf.d_fac2 + f.meta[N - 1].fac_off, sizeof(double) * (size_t)f.fac_doubles, 0,
                                sizeof(double) * (size_t)f.uni_fac_rec, (size_t)s->batch, s->stream));
-      s->buf.fold_expanded = false;
+      s->cur.expansion_outdated();
     }
     HIP_TRY(hipMemsetAsync(s->buf.d_init, 0, sizeof(double) * (size_t)s->init_doubles * s->batch, s->stream));
     // the last-but-one factor is re-created (zero) like the reference's StageFactor (:84-85): one
@@ -2297,6 +2290,7 @@ int gar_hip_cycle_append(gar_hip_solver *s, const int32_t d[5]) {
   }
   HIP_TRY(hipStreamSynchronize(s->stream));
   s->buf = {}; // (every buffer of the old layout, the lazily created ones included)
+  s->cur = {}; // (... and nothing of it is current)
   s->user_dims5 = nd;
   // the pipelined schedule belongs to the kernel family that was bound: it is re-validated against the new one (its
   // half streams and events are kept), and silently off when the new shape has no such family

@@ -2,10 +2,10 @@
 // layout of one problem (HostLayout: build_layout fills it; the caller-facing and the scratch layouts of a solver are
 // bare ones), the kernel family bound to it (KernelBinding: select_kernel resets it by value and the bind_* functions of
 // gar_select.hpp fill it) and the run state, grouped by lifetime (LayoutState, PipeState, LazyState) and held in the
-// four move-only owners below.  Included by gar_hip.cpp behind <hip/hip_runtime.h>, its standard headers (<atomic>,
-// <cstdlib>, <cstring>, <map>, <mutex>, <string>, <utility>, <vector>: none is included here) and the kernel headers;
-// internal linkage, like the rest of that unit's host code.  Ahead of them: gar_option and its two predicates, which
-// need nothing of a solver.
+// four move-only owners below, beside the one record of what is current (Current).  Included by gar_hip.cpp behind
+// <hip/hip_runtime.h>, its standard headers (<atomic>, <cstdlib>, <cstring>, <map>, <mutex>, <string>, <utility>,
+// <vector>: none is included here) and the kernel headers; internal linkage, like the rest of that unit's host code.
+// Ahead of them: gar_option and its two predicates, which need nothing of a solver.
 #pragma once
 
 namespace {
@@ -223,8 +223,7 @@ struct LayoutState {
   DevBuf<double> d_prob2, d_fac2;
   DevBuf<gar_stage_meta> d_meta2;
   DevBuf<int> d_cseg_resume;
-  bool fold_expanded = false, coupled_known = false;
-  std::vector<int> h_coupled;
+  std::vector<int> h_coupled; // (Current::know_coupled)
   // leg mode: this rank's boundary tuples and, when the legs are sharded over ranks (world > 1), the buffer every
   // rank's tuples are gathered into -- with one rank the local buffer IS the gathered one (bound_all)
   DevBuf<double> d_bound_local, d_bound_gathered, d_csol, d_cscratch;
@@ -250,25 +249,80 @@ struct LayoutState {
   size_t kkt_lds_bytes = 0;
   // gar_hip_backward_affine (gar_affine.hpp), all on the first call or none: W = Rhat^-1 [batch][horizon + 1][aff_w_rec],
   // the "re-solved" flags [batch], the offsets of the caller's affine vector [horizon + 2]; the host upload's device
-  // staging (batch vectors) on ITS first call.  aff_ready: a backward has left factor records and no matrix block was
-  // uploaded since (aff_stale names what was); aff_W_valid: W belongs to those records
+  // staging (batch vectors) on ITS first call
   DevBuf<double> d_aff_W, d_aff_in;
   DevBuf<int> d_aff_ok;
   DevBuf<long long> d_aff_off;
   int aff_w_rec = 0, aff_nx_max = 0;
   size_t aff_lds_bytes = 0, aff_prep_lds_bytes = 0;
-  bool aff_ready = false, aff_W_valid = false;
-  double aff_mueq = 0.0;
-  const char *aff_stale = nullptr;
   // gar_hip_refine (gar_refine.hpp), all on the first call or none: the right-hand side (the residual vectors), the
   // correction's ff~ / vx~, its initial stage's result, the gate words [batch]; the records' pitches and the three
-  // kernels' LDS (bytes).  ref_fwd: a roll-out has run since the last backward (there is a solution to refine)
+  // kernels' LDS (bytes)
   DevBuf<double> d_ref_rhs, d_ref_out, d_ref_init;
   DevBuf<int> d_ref_gate;
   int ref_rhs_rec = 0, ref_out_rec = 0, ref_init_rec = 0;
   long long ref_rhs_stride = 0, ref_out_stride = 0;
   size_t ref_sweep_lds_bytes = 0, ref_roll_lds_bytes = 0, ref_init_lds_bytes = 0;
-  bool ref_fwd = false;
+};
+
+// Layout lifetime, pure host state: what the device records and their host copies describe RIGHT NOW.  Four results are
+// cached -- the factor records, the side buffer W = Rhat^-1 (gar_affine.hpp), the solution in HBM, the pinned host copies
+// of the solution and of the gains (h_results) -- and every entry point that reuses one asks here whether it still may.
+// The member functions are the transitions, named after the event; none makes a HIP call (the one piece of stream
+// ordering that goes with them is settle_gains_readback, gar_hip.cpp).  A layout rebuild assigns the record whole,
+// beside `buf = {}`.  DESIGN.md 1b has the table.
+struct Current {
+  enum Factors { kNone, kOfLastBackward, kStale };
+  Factors factors = kNone;           // what gar_hip_backward_affine / gar_hip_refine may re-solve from
+  const char *stale_cause = nullptr; // kStale: the entry point that changed matrix blocks
+  double mueq = 0.0;                 // of the last backward (the fold, the re-solve's initial stage, the refinement)
+  bool W_valid = false;              // d_aff_W belongs to the factor records
+  bool expanded = false;             // folded solvers: the caller-visible factor records are formed ...
+  bool know_coupled = false;        // ... and LayoutState::h_coupled holds which problems the generic kernels took
+  bool rolled_out = false;           // a roll-out of this factorisation is enqueued: there is a solution to refine
+  bool host_solution = false;        // ... and so is its copy into h_results (gar_hip_backward_blocks, no parameter)
+  int gains_b = -1;                  // problem whose gains are in flight to / in h_results (gar_hip_prefetch_gains), -1: none
+  bool gains_collapsed = false;      // collapseFeedback ran since: stage 0's gains are fetched again
+
+  // ---- transitions ----
+  void backward_enqueued(double mu) {
+    factors = kOfLastBackward;
+    stale_cause = nullptr;
+    mueq = mu;
+    W_valid = expanded = know_coupled = rolled_out = host_solution = false;
+  }
+  void matrices_changed(const char *cause) { // (before the first backward there is nothing to make stale)
+    if (factors != kNone)
+      factors = kStale, stale_cause = cause;
+    W_valid = false;
+  }
+  void W_allocated() { W_valid = false; }
+  void W_formed() { W_valid = true; }
+  void rollout_enqueued() { rolled_out = true; }
+  void host_solution_enqueued() { host_solution = true; }
+  void solution_superseded() { host_solution = false; } // rewritten in HBM, or about to be: a fetch copies again
+  void gains_prefetched(int b) { gains_b = b, gains_collapsed = false; }
+  void gains_settled() { gains_b = -1; } // consumed or discarded
+  void feedback_collapsed() { gains_collapsed = true, host_solution = false; } // (a roll-out after it is a new one)
+  // folded solvers: the caller-visible factor records are no longer those of the family's own (collapseFeedback on a
+  // folded leg solver, a ring turn of a serial-fold solver): formed again on the next request
+  void expansion_outdated() { expanded = false; }
+  void records_expanded() { expanded = true; }
+  void coupled_read() { know_coupled = true; }
+
+  // ---- queries ----
+  bool gains_on_their_way(int b) const { return gains_b == b; }
+  bool gains_in_flight() const { return gains_b >= 0; }
+  // problem b was taken by the generic kernels (D != 0: row-major fb in its records instead of fbT2)
+  bool coupled(const std::vector<int> &h_coupled, int b) const { return know_coupled && h_coupled[(size_t)b] != 0; }
+  // why `who` cannot re-solve / refine (`verb`) from the factor records; empty: it can
+  std::string no_factors(const std::string &who, const char *verb) const {
+    if (factors == kOfLastBackward)
+      return {};
+    if (factors == kStale)
+      return who + ": matrix blocks changed since the last backward (" + stale_cause + "): call gar_hip_backward first";
+    return who + ": no backward of this solver to " + verb + " from";
+  }
 };
 
 // Solver lifetime: the pipelined sweep's half streams and events (gar_hip_set_pipeline; the serial one-wave family,

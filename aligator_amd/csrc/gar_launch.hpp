@@ -9,21 +9,6 @@ inline hipError_t stamp(gar_hip_solver *s, int i, bool when = true) {
   return s->timing && when ? hipEventRecord(s->lazy.ev[i], s->stream) : hipSuccess;
 }
 
-// gar_hip_backward_affine's state (gar_hip.h): every backward leaves factor records to re-solve from and makes W stale;
-// an upload of matrix blocks (or a cycleAppend) leaves nothing to re-solve from until the next backward
-inline void affine_note_backward(gar_hip_solver *s, double mueq) {
-  s->buf.aff_ready = true;
-  s->buf.aff_W_valid = false;
-  s->buf.aff_mueq = mueq;
-  s->buf.aff_stale = nullptr;
-  s->buf.ref_fwd = false; // (gar_hip_refine: the solution in HBM is no longer this factorisation's)
-}
-inline void affine_invalidate(gar_hip_solver *s, const char *cause) {
-  if (s->buf.aff_ready || s->buf.aff_stale) // (before the first backward there is nothing to make stale)
-    s->buf.aff_stale = cause;
-  s->buf.aff_ready = s->buf.aff_W_valid = false;
-}
-
 // MfmaParams of a stage sweep over the caller's knots: mfma_common + where the factor records go, mueq and the
 // per-launch GAR_HIP_SPD_ACCEPT.  Called as it is, this is the scratch-record form of the segment legs and the constrained
 // segment legs (fac = d_fac2): trace, init, init_stride, G0_off, g0_off, nc0, init_closed and ring0 stay ZERO there on
@@ -189,12 +174,9 @@ int backward_wave_legs(gar_hip_solver *s, double mueq, const LegChunk &c) {
   Q.leg_begin = c.l0;
   Q.boundary += c.tup_shift;
   HIP_TRY(stamp(s, 0, c.first));
-  if (s->fold) { // knots with nc > 0: fold C, d into Q, q (gar_fold.hpp); problems with D != 0 get flagged
-    s->fold_mueq = mueq;
-    s->buf.fold_expanded = s->buf.coupled_known = false;
+  if (s->fold) // knots with nc > 0: fold C, d into Q, q (gar_fold.hpp); problems with D != 0 get flagged
     hipLaunchKernelGGL(gar::gar_fold_constraints, dim3((unsigned)(s->horizon + 1), (unsigned)s->batch), dim3(256),
                        fold_lds_bytes(s), s->stream, make_fold_params(s));
-  }
   hipLaunchKernelGGL(s->leg_bwd_kernel, c.grid(s), dim3(64 * s->leg_waves), (size_t)s->leg_lds_doubles * sizeof(double),
                      s->stream, Q);
   hipLaunchKernelGGL(s->leg_tuple_kernel, c.grid(s), dim3(256), 0, s->stream, Q);
@@ -244,12 +226,9 @@ int backward_serial(gar_hip_solver *s, double mueq) {
   const gar::MfmaParams M = make_mfma_params(s, mueq);
   const gar::GenericParams I = s->serial_fold ? make_folded_params(s, mueq) : make_params(s, mueq);
   HIP_TRY(stamp(s, 0));
-  if (s->serial_fold) { // knots with nc > 0: fold C, d into Q, q in the family's knot format; problems with D != 0 get flagged
-    s->fold_mueq = mueq;
-    s->buf.fold_expanded = s->buf.coupled_known = false;
+  if (s->serial_fold) // knots with nc > 0: fold C, d into Q, q in the family's knot format; problems with D != 0 get flagged
     hipLaunchKernelGGL(gar::gar_fold_serial, dim3((unsigned)(s->horizon + 1), (unsigned)s->batch), dim3(256),
                        fold_lds_bytes(s), s->stream, make_serial_fold_params(s));
-  }
   if (s->wave_kernel) {
     const int wpb = s->waves_per_block;
     hipLaunchKernelGGL(s->wave_kernel, dim3((unsigned)((s->batch + wpb - 1) / wpb)),
@@ -432,7 +411,7 @@ int launch_forward(gar_hip_solver *s, const double *theta_dev) {
   RoctxRange range_(s->num_legs > 1 ? "gar::parallel_forward" : "gar::forwardImpl");
   const int rc = forward_by_family(s, theta_dev);
   if (rc == GAR_HIP_OK)
-    s->buf.ref_fwd = true; // (gar_hip_refine: there is a solution of this factorisation to refine)
+    s->cur.rollout_enqueued();
   return rc;
 }
 
@@ -619,18 +598,22 @@ int kkt_buffers(gar_hip_solver *s) {
   return GAR_HIP_OK;
 }
 
+// the kernel pair: a workgroup per (problem, stage), then the fold of the stage norms, a wave per problem
+int launch_kkt_pair(gar_hip_solver *s, const gar::KktParams &K) {
+  hipLaunchKernelGGL(gar::gar_kkt_stage_residuals, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)),
+                     dim3(GAR_KKT_THREADS), s->buf.kkt_lds_bytes, s->stream, K);
+  hipLaunchKernelGGL(gar::gar_kkt_reduce, dim3((unsigned)s->batch), dim3(64), 0, s->stream, K);
+  HIP_TRY(hipGetLastError());
+  return GAR_HIP_OK;
+}
+
 int launch_kkt(gar_hip_solver *s, double mueq, const double *theta_dev) {
   RoctxRange range_("gar::lqrComputeKktError");
   if (int rc = kkt_buffers(s))
     return rc;
   if (int rc = commit(s)) // knots the host staged since the last sweep
     return rc;
-  const gar::KktParams K = make_kkt_params(s, mueq, theta_dev);
-  hipLaunchKernelGGL(gar::gar_kkt_stage_residuals, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)),
-                     dim3(GAR_KKT_THREADS), s->buf.kkt_lds_bytes, s->stream, K);
-  hipLaunchKernelGGL(gar::gar_kkt_reduce, dim3((unsigned)s->batch), dim3(64), 0, s->stream, K);
-  HIP_TRY(hipGetLastError());
-  return GAR_HIP_OK;
+  return launch_kkt_pair(s, make_kkt_params(s, mueq, theta_dev));
 }
 
 // ---- the re-solve for new affine terms (gar_affine.hpp): scatter, prepare, the vector sweep, the initial stage -----------
@@ -737,7 +720,7 @@ int affine_buffers(gar_hip_solver *s) {
   s->buf.aff_nx_max = nx_max;
   s->buf.aff_lds_bytes = (size_t)lds * sizeof(double);
   s->buf.aff_prep_lds_bytes = (size_t)plds * sizeof(double);
-  s->buf.aff_W_valid = false;
+  s->cur.W_allocated();
   return GAR_HIP_OK;
 }
 
@@ -756,26 +739,31 @@ int launch_affine_scatter(gar_hip_solver *s, int b0, int nb, const double *src_d
   return GAR_HIP_OK;
 }
 
+// W = Rhat^-1 of every stage, formed once per factorisation: by the first re-solve or refinement step that needs it
+int ensure_W(gar_hip_solver *s, const gar::AffineParams &A) {
+  if (s->cur.W_valid)
+    return GAR_HIP_OK;
+  hipLaunchKernelGGL(gar::gar_affine_prepare, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)), dim3(64),
+                     s->buf.aff_prep_lds_bytes, s->stream, A);
+  HIP_TRY(hipGetLastError());
+  s->cur.W_formed();
+  return GAR_HIP_OK;
+}
+
 int launch_backward_affine(gar_hip_solver *s) {
   RoctxRange range_("gar::backward_affine");
-  s->eager_fwd = false;
-  if (s->lazy.ev_pref) { // a read-back of the previous sweep's gains may still be in flight on the second stream
-    HIP_TRY(hipStreamWaitEvent(s->stream, s->lazy.ev_pref, 0));
-    s->pref_b = -1;
-  }
+  s->cur.solution_superseded(); // (the roll-out in HBM stays a solution gar_hip_refine may start from)
+  if (int rc = settle_gains_readback(s, kBehindStream))
+    return rc;
   if (int rc = commit(s)) // (a g0 staged through gar_hip_set_init)
     return rc;
   const gar::AffineParams A = make_affine_params(s);
-  if (!s->buf.aff_W_valid) {
-    hipLaunchKernelGGL(gar::gar_affine_prepare, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)), dim3(64),
-                       s->buf.aff_prep_lds_bytes, s->stream, A);
-    HIP_TRY(hipGetLastError());
-    s->buf.aff_W_valid = true;
-  }
+  if (int rc = ensure_W(s, A))
+    return rc;
   hipLaunchKernelGGL(gar::gar_backward_affine, dim3((unsigned)s->batch), dim3(64), s->buf.aff_lds_bytes, s->stream, A);
   // the initial stage: the stand-alone kernel backward_serial launches for the families that do not fuse it, on the
   // problems the sweep took (kkt0 is factorised again: its matrix is not kept)
-  gar::GenericParams I = make_params(s, s->buf.aff_mueq);
+  gar::GenericParams I = make_params(s, s->cur.mueq);
   I.only = s->buf.d_aff_ok;
   hipLaunchKernelGGL(gar::gar_initial_wave, dim3((unsigned)s->batch), dim3(64),
                      (size_t)gar::gar_initial_wave_lds_doubles(s->n0, s->nth0) * sizeof(double), s->stream, I);
@@ -828,36 +816,28 @@ int refine_buffers(gar_hip_solver *s) {
 // the KKT buffers of the solution in HBM (what gar_hip_kkt_error_async writes, at the mueq of the backward being reused),
 // the residual vectors into the right-hand side and the gate words of the next step
 int launch_refine_residual(gar_hip_solver *s, double threshold) {
-  gar::KktParams K = make_kkt_params(s, s->buf.aff_mueq, nullptr);
+  gar::KktParams K = make_kkt_params(s, s->cur.mueq, nullptr);
   K.rhs = s->buf.d_ref_rhs;
   K.gate = s->buf.d_ref_gate;
   K.status = status_words(s);
   K.rhs_stride = s->buf.ref_rhs_stride;
   K.rhs_rec = s->buf.ref_rhs_rec;
   K.threshold = threshold;
-  hipLaunchKernelGGL(gar::gar_kkt_stage_residuals, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)),
-                     dim3(GAR_KKT_THREADS), s->buf.kkt_lds_bytes, s->stream, K);
-  hipLaunchKernelGGL(gar::gar_kkt_reduce, dim3((unsigned)s->batch), dim3(64), 0, s->stream, K);
-  HIP_TRY(hipGetLastError());
-  return GAR_HIP_OK;
+  return launch_kkt_pair(s, K);
 }
 
 // the correction of the gated problems, added to the solution records
 int launch_refine_correction(gar_hip_solver *s) {
   gar::AffineParams A = make_affine_params(s);
-  if (!s->buf.aff_W_valid) {
-    hipLaunchKernelGGL(gar::gar_affine_prepare, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)), dim3(64),
-                       s->buf.aff_prep_lds_bytes, s->stream, A);
-    HIP_TRY(hipGetLastError());
-    s->buf.aff_W_valid = true;
-  }
+  if (int rc = ensure_W(s, A))
+    return rc;
   A.rhs = s->buf.d_ref_rhs;
   A.out = s->buf.d_ref_out;
   A.gate = s->buf.d_ref_gate;
   A.rhs_stride = s->buf.ref_rhs_stride, A.out_stride = s->buf.ref_out_stride;
   A.rhs_rec = s->buf.ref_rhs_rec, A.out_rec = s->buf.ref_out_rec;
   gar::RefineParams R{};
-  R.G = make_params(s, s->buf.aff_mueq);
+  R.G = make_params(s, s->cur.mueq);
   R.rhs = A.rhs, R.out = A.out, R.init = s->buf.d_ref_init, R.gate = A.gate;
   R.rhs_stride = A.rhs_stride, R.out_stride = A.out_stride, R.init_rec = s->buf.ref_init_rec;
   R.rhs_rec = A.rhs_rec, R.out_rec = A.out_rec;

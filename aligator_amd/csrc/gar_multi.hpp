@@ -251,7 +251,6 @@ int multi_num_failed(gar_hip_solver *s) {
   int n = 0;
   for (int v : acc)
     n += (v != 0);
-  s->last_failed = n;
   return n;
 }
 

@@ -59,12 +59,9 @@ int pipe_fork(gar_hip_solver *s, bool again = false) {
 }
 int pipe_backward(gar_hip_solver *s, double mueq) {
   RoctxRange range_("gar::backwardImpl+factor_initial (pipelined)");
-  s->eager_fwd = false;
-  affine_note_backward(s, mueq);
-  if (s->lazy.ev_pref) {
-    HIP_TRY(hipStreamWaitEvent(s->stream, s->lazy.ev_pref, 0));
-    s->pref_b = -1;
-  }
+  s->cur.backward_enqueued(mueq);
+  if (int rc = settle_gains_readback(s, kBehindStream))
+    return rc;
   if (s->buf.dirty) { // staged host data goes out on the caller's stream: order it, then fork again
     if (int rc = pipe_join(s))
       return rc;
@@ -135,7 +132,7 @@ int pipe_forward(gar_hip_solver *s) {
     if (s->timing)
       HIP_TRY(hipEventRecord(s->pipe.evT[h][3], st));
   }
-  s->buf.ref_fwd = true; // (gar_hip_refine: there is a solution of this factorisation to refine)
+  s->cur.rollout_enqueued();
   return GAR_HIP_OK;
 }
 

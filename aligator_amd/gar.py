@@ -616,6 +616,10 @@ class BatchedRiccatiSolver:
         fb = buf[int(offs[2]):total] if gains else None
         return sol, ff, fb
 
+    def prefetch_gains(self, b: int = 0):
+        """gar_hip_prefetch_gains: the gains' read-back of problem b started on a second stream; fetch_results waits for it"""
+        self._check(self._L.gar_hip_prefetch_gains(self._h, int(b)))
+
     def gains_all(self, b: int = 0):
         """-> ([ff_t], [fb_t]) for every stage t, fb_t of shape (nu+nc+nx2, nx) (StageFactor's row-major
         fb), through the bulk path; the same values gar_hip_get_gains returns stage by stage."""
