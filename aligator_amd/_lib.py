@@ -75,6 +75,11 @@ SIGNATURES = {
     "gar_hip_backward_affine_async": (C.c_int, [C.c_void_p]),
     "gar_hip_refine_async": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     "gar_hip_refine": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _PI32]),
+    "gar_hip_upload_packed_user_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "gar_hip_solution_vectors_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "gar_hip_adjoint_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gar_hip_adjoint": (C.c_int, [C.c_void_p, _PD, _PD, _PD]),
+    "gar_hip_device_adjoints": (C.c_void_p, [C.c_void_p]),
     "gar_hip_slow_path_stages": (C.c_int, [C.c_void_p, _PI64]),
     "gar_hip_constrained_bk_stages": (C.c_int, [C.c_void_p, _PI64]),
     "gar_hip_boundary_doubles": (C.c_int64, [C.c_void_p]),

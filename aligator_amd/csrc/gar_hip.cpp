@@ -36,6 +36,7 @@
 #include "gar_kkt.hpp"
 #include "gar_affine.hpp"
 #include "gar_refine.hpp"
+#include "gar_adjoint.hpp"
 #include "gar_host.hpp"
 #include "gar_record_io.hpp"
 
@@ -1773,6 +1774,93 @@ int gar_hip_refine(gar_hip_solver *s, int max_steps, double threshold, int32_t o
     out2[1] = remaining;
   }
   return failure_epilogue(s, "refine");
+}
+
+// ---- gradients of a resident batch (gar_adjoint.hpp; launches in gar_launch.hpp) -----------------------------------------
+int gar_hip_upload_packed_user_device(gar_hip_solver *s, int b0, int nb, const double *packed_user_dev) {
+  GAR_GUARD(s);
+  if (int rc = affine_check(s, "gar_hip_upload_packed_user_device"))
+    return rc;
+  if (!packed_user_dev || b0 < 0 || nb < 0 || b0 + nb > s->batch)
+    return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_packed_user_device: bad argument");
+  if (int rc = user_layout_buffers(s))
+    return rc;
+  if (int rc = commit(s)) // staged host data first, then the device copy wins
+    return rc;
+  s->cur.matrices_changed("gar_hip_upload_packed_user_device");
+  return launch_user_upload(s, b0, nb, packed_user_dev);
+}
+
+int gar_hip_solution_vectors_device(gar_hip_solver *s, int b0, int nb, double *out_dev) {
+  GAR_GUARD(s); // (a pipelined sweep: the solver's stream is ordered behind the half streams first)
+  if (int rc = affine_check(s, "gar_hip_solution_vectors_device"))
+    return rc;
+  if (!out_dev || b0 < 0 || nb < 0 || b0 + nb > s->batch)
+    return fail(GAR_HIP_ERR_ARG, "gar_hip_solution_vectors_device: bad argument");
+  if (int rc = affine_buffers(s))
+    return rc;
+  if (int rc = user_layout_buffers(s))
+    return rc;
+  return launch_solution_gather(s, b0, nb, s->buf.d_sol, out_dev);
+}
+
+namespace {
+// who is served and the state an adjoint needs; then the buffers (first call)
+int adjoint_begin(gar_hip_solver *s, const void *cot, const void *grad, const char *who) {
+  if (int rc = affine_check(s, who))
+    return rc;
+  const std::string w(who);
+  if (!cot)
+    return fail(GAR_HIP_ERR_ARG, w + ": null cotangent");
+  if (reinterpret_cast<uintptr_t>(grad) & 15)
+    return fail(GAR_HIP_ERR_ARG, w + ": the gradient records must start on a 16-byte boundary");
+  const std::string refusal = s->cur.no_factors(w, "differentiate");
+  if (!refusal.empty())
+    return fail(GAR_HIP_ERR_ARG, refusal);
+  if (!s->cur.rolled_out)
+    return fail(GAR_HIP_ERR_ARG, w + ": no forward since the last backward (there is no solution to differentiate)");
+  if (int rc = affine_buffers(s))
+    return rc;
+  if (int rc = refine_buffers(s))
+    return rc;
+  if (int rc = adjoint_buffers(s))
+    return rc;
+  return commit(s); // (a g0 staged through gar_hip_set_init)
+}
+} // namespace
+
+int gar_hip_adjoint_async(gar_hip_solver *s, const double *cot_dev, double *adj_out_dev, double *grad_out_dev) {
+  GAR_GUARD(s); // (a pipelined sweep: the solver's stream is ordered behind the half streams first)
+  if (int rc = adjoint_begin(s, cot_dev, grad_out_dev, "gar_hip_adjoint_async"))
+    return rc;
+  return launch_adjoint(s, cot_dev, adj_out_dev, grad_out_dev);
+}
+
+int gar_hip_adjoint(gar_hip_solver *s, const double *cot_host, double *adj_host, double *grad_host) {
+  GAR_GUARD(s);
+  if (int rc = adjoint_begin(s, cot_host, nullptr, "gar_hip_adjoint"))
+    return rc;
+  const size_t n = (size_t)affine_offsets(s, nullptr) * (size_t)s->batch;
+  const size_t ng = (size_t)caller_layout(s).prob_doubles * (size_t)s->batch;
+  if (!s->buf.d_adj_vec)
+    HIP_TRY(s->buf.d_adj_vec.alloc(2 * n + 2));
+  if (grad_host && !s->buf.d_adj_grad)
+    HIP_TRY(s->buf.d_adj_grad.alloc(ng));
+  double *cot = s->buf.d_adj_vec, *adj = cot + n;
+  HIP_TRY(hipMemcpyAsync(cot, cot_host, sizeof(double) * n, hipMemcpyHostToDevice, s->stream));
+  if (int rc = launch_adjoint(s, cot, adj_host ? adj : nullptr, grad_host ? s->buf.d_adj_grad.get() : nullptr))
+    return rc;
+  if (int rc = d2h(s, adj_host, adj, (int64_t)n))
+    return rc;
+  if (int rc = d2h(s, grad_host, s->buf.d_adj_grad, (int64_t)ng))
+    return rc;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return failure_epilogue(s, "adjoint");
+}
+
+const double *gar_hip_device_adjoints(gar_hip_solver *s) {
+  pipe_autojoin(s);
+  return s && !s->multi ? s->buf.d_adj_rec.get() : nullptr;
 }
 
 int gar_hip_get_status(gar_hip_solver *s, int32_t *out) {

@@ -263,6 +263,15 @@ struct LayoutState {
   int ref_rhs_rec = 0, ref_out_rec = 0, ref_init_rec = 0;
   long long ref_rhs_stride = 0, ref_out_stride = 0;
   size_t ref_sweep_lds_bytes = 0, ref_roll_lds_bytes = 0, ref_init_lds_bytes = 0;
+  // gar_hip_adjoint (gar_adjoint.hpp).  A padded solver's caller-side knot offsets [horizon + 1], on the first call that
+  // speaks the caller's packed layout on the device (the upload scatter, the gradient kernel).  The adjoint records
+  // [batch][sol_doubles] and the gate words [batch], both on the first adjoint or neither; the gradient kernel's LDS
+  // (bytes).  The synchronous form's device staging on ITS first call: cotangents | adjoints, and the gradient records
+  // on the first call that asks for them.  (Right-hand side, ff~ / vx~ and the initial stage's result: the refinement's.)
+  DevBuf<long long> d_adj_uoff;
+  DevBuf<double> d_adj_rec, d_adj_vec, d_adj_grad;
+  DevBuf<int> d_adj_gate;
+  size_t adj_grad_lds_bytes = 0;
 };
 
 // Layout lifetime, pure host state: what the device records and their host copies describe RIGHT NOW.  Four results are

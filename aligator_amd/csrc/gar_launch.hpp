@@ -826,26 +826,157 @@ int launch_refine_residual(gar_hip_solver *s, double threshold) {
   return launch_kkt_pair(s, K);
 }
 
-// the correction of the gated problems, added to the solution records
-int launch_refine_correction(gar_hip_solver *s) {
-  gar::AffineParams A = make_affine_params(s);
-  if (int rc = ensure_W(s, A))
-    return rc;
+// the parameter blocks of the redirected sweep, its initial stage and its roll-out: the refinement's side buffers, the
+// gate words of the caller (the refinement's, or the adjoint's "status word zero")
+void make_refine_params(gar_hip_solver *s, const int *gate, gar::AffineParams &A, gar::RefineParams &R) {
+  A = make_affine_params(s);
   A.rhs = s->buf.d_ref_rhs;
   A.out = s->buf.d_ref_out;
-  A.gate = s->buf.d_ref_gate;
+  A.gate = gate;
   A.rhs_stride = s->buf.ref_rhs_stride, A.out_stride = s->buf.ref_out_stride;
   A.rhs_rec = s->buf.ref_rhs_rec, A.out_rec = s->buf.ref_out_rec;
-  gar::RefineParams R{};
+  R = gar::RefineParams{};
   R.G = make_params(s, s->cur.mueq);
   R.rhs = A.rhs, R.out = A.out, R.init = s->buf.d_ref_init, R.gate = A.gate;
   R.rhs_stride = A.rhs_stride, R.out_stride = A.out_stride, R.init_rec = s->buf.ref_init_rec;
   R.rhs_rec = A.rhs_rec, R.out_rec = A.out_rec;
   R.fb_t2 = A.fb_t2, R.nx_max = A.nx_max;
+}
+
+// the correction of the gated problems, added to the solution records
+int launch_refine_correction(gar_hip_solver *s) {
+  gar::AffineParams A;
+  gar::RefineParams R;
+  make_refine_params(s, s->buf.d_ref_gate, A, R);
+  if (int rc = ensure_W(s, A))
+    return rc;
   const dim3 grid((unsigned)s->batch), wave(64);
   hipLaunchKernelGGL(gar::gar_refine_sweep, grid, wave, s->buf.ref_sweep_lds_bytes, s->stream, A);
   hipLaunchKernelGGL(gar::gar_refine_initial, grid, wave, s->buf.ref_init_lds_bytes, s->stream, R);
   hipLaunchKernelGGL(gar::gar_refine_rollout, grid, wave, s->buf.ref_roll_lds_bytes, s->stream, R);
   HIP_TRY(hipGetLastError());
+  return GAR_HIP_OK;
+}
+
+// ---- gradients of a resident batch (gar_adjoint.hpp): the caller's packed layout on the device, the adjoint solve -------
+// a padded solver's caller-side knot offsets on the device (the caller's layout does not turn with the ring); an unpadded
+// solver's are the device's own stage descriptors
+int user_layout_buffers(gar_hip_solver *s) {
+  if (!s->padded || s->buf.d_adj_uoff)
+    return GAR_HIP_OK;
+  std::vector<long long> off;
+  for (const gar_stage_meta &m : s->ulay->meta)
+    off.push_back(m.in_off);
+  DevBuf<long long> d;
+  HIP_TRY(d.alloc(off.size()));
+  HIP_TRY(hipMemcpy(d, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice));
+  s->buf.d_adj_uoff = std::move(d);
+  return GAR_HIP_OK;
+}
+
+// (affine_buffers ran: the offsets of the affine layout are on the device)
+gar::AdjointParams make_adjoint_params(gar_hip_solver *s) {
+  const gar::HostLayout &u = caller_layout(s);
+  gar::AdjointParams P{};
+  P.meta = s->buf.d_meta;
+  P.U.in_off = s->padded ? s->buf.d_adj_uoff.get() : nullptr;
+  P.U.stride = u.prob_doubles, P.U.G0_off = u.G0_off, P.U.g0_off = u.g0_off;
+  P.U.unx = s->padded ? s->unx : 0, P.U.unu = s->padded ? s->unu : 0;
+  P.U.nc0 = s->user_nc0;
+  P.vec_off = s->buf.d_aff_off;
+  P.vec_stride = affine_offsets(s, nullptr);
+  P.status = status_words(s);
+  P.rhs = s->buf.d_ref_rhs;
+  P.gate = s->buf.d_adj_gate;
+  P.rhs_stride = s->buf.ref_rhs_stride;
+  P.rhs_rec = s->buf.ref_rhs_rec;
+  P.sol = s->buf.d_sol;
+  P.adj = s->buf.d_adj_rec;
+  P.sol_stride = s->sol_doubles;
+  P.prob = s->buf.d_prob;
+  P.prob_stride = s->prob_doubles, P.G0_off = s->G0_off, P.g0_off = s->g0_off;
+  P.horizon = s->horizon, P.nc0 = s->nc0, P.nx0 = s->nx0;
+  P.qr_packed = s->qr_packed ? 1 : 0;
+  return P;
+}
+
+// the adjoint records, the gate words and the LDS of the two kernels with dynamic LDS, on the first call after the layout
+// was built (affine_buffers and refine_buffers ran)
+int adjoint_buffers(gar_hip_solver *s) {
+  if (s->buf.d_adj_gate)
+    return GAR_HIP_OK;
+  if (int rc = user_layout_buffers(s))
+    return rc;
+  int glds = 0;
+  for (const gar_stage_meta &m : s->meta) // (the device's dimensions bound the caller's)
+    glds = std::max(glds, gar::adjoint_grad_lds_doubles(m.nx, m.nu, m.nx2, s->nc0, s->nx0));
+  if ((size_t)glds * sizeof(double) > kCuLdsBytes)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_adjoint: a knot of the gradient record needs " +
+                                             std::to_string((size_t)glds * sizeof(double)) + " B of LDS (> 160 KiB per CU)");
+  HIP_TRY(max_lds(gar::gar_adjoint_gradients, (size_t)glds));
+  HIP_TRY(max_lds(gar::gar_adjoint_rollout, s->buf.ref_roll_lds_bytes / sizeof(double)));
+  DevBuf<double> rec;
+  DevBuf<int> gate;
+  HIP_TRY(rec.zalloc((size_t)s->batch * (size_t)s->sol_doubles));
+  HIP_TRY(gate.zalloc((size_t)s->batch));
+  s->buf.d_adj_rec = std::move(rec);
+  s->buf.d_adj_gate = std::move(gate);
+  s->buf.adj_grad_lds_bytes = (size_t)glds * sizeof(double);
+  return GAR_HIP_OK;
+}
+
+// nb packed problems in the caller's layout at the DEVICE address src into the knots of problems b0 ...
+int launch_user_upload(gar_hip_solver *s, int b0, int nb, const double *src_dev) {
+  if (nb == 0)
+    return GAR_HIP_OK;
+  gar::AdjointParams P = make_adjoint_params(s);
+  P.user = src_dev;
+  P.b0 = b0;
+  hipLaunchKernelGGL(gar::gar_user_upload_scatter, dim3((unsigned)nb * (unsigned)(s->horizon + 1)), dim3(GAR_ADJ_THREADS), 0,
+                     s->stream, P);
+  HIP_TRY(hipGetLastError());
+  return GAR_HIP_OK;
+}
+
+// records (the solution's or the adjoint's) of problems b0 ... as nb vectors of the affine layout at the DEVICE address out
+int launch_solution_gather(gar_hip_solver *s, int b0, int nb, const double *rec_dev, double *out_dev) {
+  if (nb == 0)
+    return GAR_HIP_OK;
+  gar::AdjointParams P = make_adjoint_params(s);
+  P.rec = rec_dev;
+  P.vec = out_dev;
+  P.b0 = b0;
+  hipLaunchKernelGGL(gar::gar_solution_gather, dim3((unsigned)nb * (unsigned)(s->horizon + 1)), dim3(64), 0, s->stream, P);
+  HIP_TRY(hipGetLastError());
+  return GAR_HIP_OK;
+}
+
+// the cotangents at cot_dev -> the adjoint records; their affine-layout vectors to adj_dev and the gradient records to
+// grad_dev where asked for.  Nothing of the primal is written.
+int launch_adjoint(gar_hip_solver *s, const double *cot_dev, double *adj_dev, double *grad_dev) {
+  RoctxRange range_("gar::adjoint");
+  gar::AffineParams A;
+  gar::RefineParams R;
+  make_refine_params(s, s->buf.d_adj_gate, A, R);
+  gar::RefineParams Radj = R; // the roll-out's "solution" is the adjoint record
+  Radj.G.sol = s->buf.d_adj_rec;
+  if (int rc = ensure_W(s, A))
+    return rc;
+  gar::AdjointParams P = make_adjoint_params(s);
+  P.cot = cot_dev;
+  P.grad = grad_dev;
+  const dim3 grid((unsigned)s->batch), stages((unsigned)s->batch * (unsigned)(s->horizon + 1)), wave(64);
+  hipLaunchKernelGGL(gar::gar_adjoint_scatter, stages, wave, 0, s->stream, P);
+  hipLaunchKernelGGL(gar::gar_refine_sweep, grid, wave, s->buf.ref_sweep_lds_bytes, s->stream, A);
+  hipLaunchKernelGGL(gar::gar_refine_initial, grid, wave, s->buf.ref_init_lds_bytes, s->stream, R);
+  hipLaunchKernelGGL(gar::gar_adjoint_rollout, grid, wave, s->buf.ref_roll_lds_bytes, s->stream, Radj);
+  HIP_TRY(hipGetLastError());
+  if (adj_dev)
+    if (int rc = launch_solution_gather(s, 0, s->batch, s->buf.d_adj_rec, adj_dev))
+      return rc;
+  if (grad_dev) {
+    hipLaunchKernelGGL(gar::gar_adjoint_gradients, stages, dim3(GAR_ADJ_THREADS), s->buf.adj_grad_lds_bytes, s->stream, P);
+    HIP_TRY(hipGetLastError());
+  }
   return GAR_HIP_OK;
 }

@@ -58,10 +58,26 @@ __host__ __device__ inline int refine_rollout_lds_doubles(int nx_max, int nx, in
   const int fb = fb_t2 ? ((nx + 1) / 2) * (2 * nr + 2) : nr * nx;
   return 2 * ((nx_max + 1) & ~1) + (fb + 2) + (nr + 2) + (nvv + 2) + (nx2 + 2);
 }
-__global__ void __launch_bounds__(64) gar_refine_rollout(RefineParams R) {
+// One kernel template, two instances.  gar_rollout<false> is gar_refine_rollout.  gar_rollout<true> is gar_adjoint_rollout
+// (gar_adjoint.hpp): the same recursion with dx, du, dl STORED instead of added -- R.G.sol then names the adjoint records
+// (the solution records' layout and pitch) -- and a record of exact zeros for a problem the gate leaves out.  (The body
+// stands in the kernel itself, not in a device function the kernel calls: that is what keeps the instructions of the
+// <false> instance those of the kernel it replaces.)
+#define GAR_ROLLOUT_PUT(p, v)                                                                                            \
+  do {                                                                                                                   \
+    if constexpr (ADJOINT)                                                                                               \
+      (p) = (v);                                                                                                         \
+    else                                                                                                                 \
+      (p) += (v);                                                                                                        \
+  } while (0)
+template <bool ADJOINT> __global__ void __launch_bounds__(64) gar_rollout(RefineParams R) {
   const int b = (int)blockIdx.x, lane = (int)threadIdx.x, N = R.G.horizon;
-  if (R.gate[b] == 0)
+  if (R.gate[b] == 0) {
+    if constexpr (ADJOINT)
+      for (long long e = lane; e < R.G.sol_stride; e += 64)
+        R.G.sol[(long long)b * R.G.sol_stride + e] = 0.0;
     return;
+  }
   const double *factors = R.G.fac + (long long)b * R.G.fac_stride;
   const double *outb = R.out + (long long)b * R.out_stride;
   double *sol = R.G.sol + (long long)b * R.G.sol_stride;
@@ -73,10 +89,10 @@ __global__ void __launch_bounds__(64) gar_refine_rollout(RefineParams R) {
     for (int i = lane; i < m0.nx; i += 64) {
       const double v = io[i];
       dx[i] = v;
-      sol[m0.x_off + i] += v;
+      GAR_ROLLOUT_PUT(sol[m0.x_off + i], v);
     }
     for (int k = lane; k < R.G.nc0; k += 64)
-      sol[m0.l_off + k] += io[m0.nx + k];
+      GAR_ROLLOUT_PUT(sol[m0.l_off + k], io[m0.nx + k]);
   }
   wave_sync();
   for (int t = 0; t <= N; ++t) {
@@ -131,10 +147,10 @@ __global__ void __launch_bounds__(64) gar_refine_rollout(RefineParams R) {
           acc += rp[j] * dx[j];
       }
       if (r < nu) {
-        sol[m.u_off + r] += acc;
+        GAR_ROLLOUT_PUT(sol[m.u_off + r], acc);
       } else {
         dxn[r - nu] = acc;
-        sol[mn.x_off + (r - nu)] += acc;
+        GAR_ROLLOUT_PUT(sol[mn.x_off + (r - nu)], acc);
       }
     }
     wave_sync();
@@ -147,7 +163,7 @@ __global__ void __launch_bounds__(64) gar_refine_rollout(RefineParams R) {
         const int fj = pk ? (2 * j < n2 ? j * n2 : (n2 - 1 - j) * (n2 + 1) + 1) : j * n2;
         acc += Vs[i >= j ? fj + i : fi + j] * dxn[j];
       }
-      sol[mn.l_off + i] += acc;
+      GAR_ROLLOUT_PUT(sol[mn.l_off + i], acc);
     }
     double *tmp = dx;
     dx = dxn;
@@ -156,5 +172,7 @@ __global__ void __launch_bounds__(64) gar_refine_rollout(RefineParams R) {
     wave_sync();
   }
 }
+#undef GAR_ROLLOUT_PUT
+constexpr auto gar_refine_rollout = &gar_rollout<false>; // the correction of a refinement step, added in place
 
 } // namespace gar

@@ -530,6 +530,48 @@ class BatchedRiccatiSolver:
         """gar_hip_refine_async: exactly `steps` steps enqueued, not waited for; the threshold gates on the device"""
         self._check(self._L.gar_hip_refine_async(self._h, int(steps), float(threshold)))
 
+    # ---- gradients of the resident batch (gar_hip_adjoint, csrc/gar_adjoint.hpp) ---------------------------------------
+    def upload_packed_user_device(self, ptr: int, b0: int = 0, nb: Optional[int] = None):
+        """gar_hip_upload_packed_user_device: `ptr` is the device address of nb packed problems in the CALLER's layout
+        (pack()'s: `problem_doubles` each); enqueued, not waited for"""
+        nb = self.batch - b0 if nb is None else nb
+        self._factors_cache = {}
+        self._check(self._L.gar_hip_upload_packed_user_device(self._h, int(b0), int(nb), C.c_void_p(ptr)))
+
+    def solution_vectors_device(self, ptr: int, b0: int = 0, nb: Optional[int] = None):
+        """gar_hip_solution_vectors_device: the solutions of problems b0 ... as nb vectors of the affine layout (x_t | u_t
+        | lbd_{t+1} per stage, then lbd0; `affine_doubles` each) at the device address `ptr`; enqueued, not waited for"""
+        nb = self.batch - b0 if nb is None else nb
+        self._check(self._L.gar_hip_solution_vectors_device(self._h, int(b0), int(nb), C.c_void_p(ptr)))
+
+    def adjoint(self, cot: np.ndarray, want_grad: bool = True):
+        """gar_hip_adjoint: cot holds `batch` cotangent vectors of the affine layout (dL/dx_t | dL/du_t | dL/dlbd_{t+1} per
+        stage, then dL/dlbd0).  -> (adj, grad): adj (batch, affine_doubles) is the adjoint d, the gradient with respect to
+        q, r, f, g0 in the same layout; grad (batch, problem_doubles) the gradient with respect to every block, a packed
+        problem each (unpack_gradient), or None.  Nothing of the primal is written."""
+        cot = np.ascontiguousarray(cot, dtype=np.float64).reshape(-1)
+        n = self.affine_doubles
+        if cot.size != n * self.batch:
+            raise ValueError(f"{cot.size} entries, expected batch x affine_doubles = {n * self.batch}")
+        adj = np.zeros((self.batch, n))
+        grad = np.zeros((self.batch, self.problem_doubles)) if want_grad else None
+        self._check(self._L.gar_hip_adjoint(self._h, _ptr(cot), _ptr(adj), _ptr(grad)))
+        return adj, grad
+
+    def adjoint_async(self, cot_ptr: int, adj_ptr: int = 0, grad_ptr: int = 0):
+        """gar_hip_adjoint_async: device addresses (adj_ptr, grad_ptr: 0 = not wanted); enqueued, not waited for"""
+        self._check(self._L.gar_hip_adjoint_async(self._h, C.c_void_p(cot_ptr), C.c_void_p(adj_ptr or None),
+                                                  C.c_void_p(grad_ptr or None)))
+
+    def device_adjoints(self):
+        """device address of the adjoint records of the last adjoint ([batch][device_solution_doubles], the device solution
+        records' layout); None before the first adjoint"""
+        return self._L.gar_hip_device_adjoints(self._h)
+
+    def unpack_gradient(self, buf: np.ndarray) -> LqrProblem:
+        """one gradient record of adjoint() as an LqrProblem whose blocks are the gradients of the same-named blocks"""
+        return self.unpack(np.asarray(buf, dtype=np.float64).reshape(-1))
+
     def slow_path_stages(self):
         """(stages of the last backward that left the register LDL^T because Rhat failed the first
         Bunch-Kaufman test, those of them where Bunch-Kaufman really pivoted), summed over the batch."""

@@ -410,6 +410,57 @@ int gar_hip_backward_affine_async(gar_hip_solver *s);
 int gar_hip_refine_async(gar_hip_solver *s, int steps, double threshold);
 int gar_hip_refine(gar_hip_solver *s, int max_steps, double threshold, int32_t out2[2] /* may be NULL */);
 
+/* ---- gradients of the resident batch: the adjoint solve and the block gradients (csrc/gar_adjoint.hpp) ----------------
+ * With K z = -b the KKT system of the problem (z = (lbd0, x_t, u_t, lbd_{t+1} ...), b = (g0, q_t, r_t, f_t ...)) and
+ * g = dL/dz the cotangent of a scalar loss L(z), the adjoint d = (dlbd0, dx_t, du_t, dlbd_{t+1} ...) is the LQ solution for
+ * the SAME matrices and the affine terms g: the re-solve's vector sweep from fb, Vxx and W on the cotangents, the initial
+ * stage, and a roll-out that stores d in a record of its own.  Then
+ *   dL/dq = dx  dL/dr = du  dL/df = dlbd'  dL/dg0 = dlbd0
+ *   dL/dQ = 1/2 (dx x^T + x dx^T)  dL/dR = 1/2 (du u^T + u du^T)  dL/dS = dx u^T + x du^T
+ *   dL/dA = dlbd' x^T + lbd' dx^T  dL/dB = dlbd' u^T + lbd' du^T  dL/dG0 = dlbd0 x0^T + lbd0 dx0^T
+ * (Q and R as symmetric matrices: both triangles, bitwise symmetric; a terminal knot has no A, B, f: zeros where its
+ * record keeps the slots).
+ *   gar_hip_adjoint_async   cot_dev: batch cotangent vectors in the layout of gar_hip_affine_doubles -- per stage the
+ *                           cotangents of x_t | u_t | lbd_{t+1}, then of lbd0, the caller's dimensions (a terminal knot's
+ *                           f slot, where the layout has one, is ignored).  adj_out_dev (may be NULL): batch vectors of
+ *                           the same layout, d -- which is the gradient with respect to q, r, f, g0 (a terminal f slot:
+ *                           zero).  grad_out_dev (may be NULL: the gradient kernel is not launched; 16-byte aligned):
+ *                           batch records of gar_hip_problem_doubles in the layout gar_hip_upload_packed takes -- G0 | g0
+ *                           | knots, each knot Q S R q r A B f, every block full and column-major, the caller's
+ *                           dimensions -- the whole gradient of one packed problem, the pads between records zero.
+ *                           Enqueued on the solver's stream (behind the half streams of a pipelined sweep), no host wait.
+ *   gar_hip_adjoint         the same from and to HOST arrays (device staging allocated by the first call); synchronous,
+ *                           returns like gar_hip_backward_affine (GAR_HIP_ERR_FACTOR when a status word is non-zero).
+ * A problem whose status word is non-zero gets an adjoint and a gradient record of exact zeros.
+ * What keeps its bits: EVERYTHING of the primal -- knots, factor records, gains, solution records, status words, the KKT
+ * buffers, W (formed first if it is stale, as for a refinement step) and the host copies of solution and gains.  The
+ * right-hand side, ff~ / vx~ and the initial stage's result go through the refinement's side buffers, the adjoint records
+ * and gate words are the adjoint's own (allocated by the first call: gar_hip_debug_alloc_count rises then and not
+ * again); a refinement step before or after gives the bits it gives without the adjoint.
+ * State (otherwise GAR_HIP_ERR_ARG naming the reason, nothing launched): a non-null cotangent, a backward whose matrix
+ * blocks are still current, a forward since that backward.  Served: exactly who gar_hip_backward_affine serves; everyone
+ * else answers GAR_HIP_ERR_UNSUPPORTED with nothing launched and nothing touched.
+ *
+ * For a device-resident caller that speaks the caller's dimensions throughout (aligator_amd/layer.py):
+ *   gar_hip_upload_packed_user_device  nb packed problems in the CALLER's layout (gar_hip_upload_packed's) at a device
+ *                           address into the knots of problems b0 ...: Q / R packed where the family keeps lower
+ *                           triangles, the dummy rows and columns of a padded solver written.  Enqueued, not waited for;
+ *                           to the run state it is gar_hip_upload_packed_device (staged host blocks go out first; the
+ *                           factorisation is stale until the next backward).
+ *   gar_hip_solution_vectors_device    the solutions of problems b0 ... as nb vectors of the affine layout, x_t | u_t |
+ *                           lbd_{t+1} per stage, then lbd0, at a device address.  Enqueued, not waited for.
+ * Both serve who the adjoint serves. */
+int gar_hip_upload_packed_user_device(gar_hip_solver *s, int b0, int nb, const double *packed_user_dev);
+int gar_hip_solution_vectors_device(gar_hip_solver *s, int b0, int nb, double *out_dev);
+int gar_hip_adjoint_async(gar_hip_solver *s, const double *cot_dev, double *adj_out_dev /* may be NULL */,
+                          double *grad_out_dev /* may be NULL */);
+int gar_hip_adjoint(gar_hip_solver *s, const double *cot_host, double *adj_host /* may be NULL */,
+                    double *grad_host /* may be NULL */);
+/* the adjoint records of the last adjoint, [batch][the device's solution-record doubles] in the device solution records'
+ * layout (gar_hip_device_stage_layout: x, u, lbda offsets; a padded solver's dummy entries are exact zeros); NULL before
+ * the first adjoint and on a multi-device handle */
+const double *gar_hip_device_adjoints(gar_hip_solver *s);
+
 /* Diagnostics of the last backward (specialised kernel families; no reference counterpart): the
  * register LDL^T of Rhat is what Bunch-Kaufman does whenever its first test |a_kk| >= alpha*colmax
  * holds at every column (bunchkaufman.hpp:61); out[0] = stages (summed over the batch) where it did
