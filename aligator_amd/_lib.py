@@ -80,6 +80,8 @@ SIGNATURES = {
     "gar_hip_adjoint_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gar_hip_adjoint": (C.c_int, [C.c_void_p, _PD, _PD, _PD]),
     "gar_hip_device_adjoints": (C.c_void_p, [C.c_void_p]),
+    "gar_hip_affine_solve_multi_async": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gar_hip_affine_solve_multi": (C.c_int, [C.c_void_p, C.c_int, _PD, _PD]),
     "gar_hip_slow_path_stages": (C.c_int, [C.c_void_p, _PI64]),
     "gar_hip_constrained_bk_stages": (C.c_int, [C.c_void_p, _PI64]),
     "gar_hip_boundary_doubles": (C.c_int64, [C.c_void_p]),

@@ -37,6 +37,7 @@
 #include "gar_affine.hpp"
 #include "gar_refine.hpp"
 #include "gar_adjoint.hpp"
+#include "gar_affine_multi.hpp"
 #include "gar_host.hpp"
 #include "gar_record_io.hpp"
 
@@ -1861,6 +1862,60 @@ int gar_hip_adjoint(gar_hip_solver *s, const double *cot_host, double *adj_host,
 const double *gar_hip_device_adjoints(gar_hip_solver *s) {
   pipe_autojoin(s);
   return s && !s->multi ? s->buf.d_adj_rec.get() : nullptr;
+}
+
+// ---- many affine terms at once (gar_affine_multi.hpp; launches in gar_launch.hpp) --------------------------------------------
+namespace {
+// who is served and the state the solve needs (gar_hip_backward_affine's; no forward: the primal solution is not read);
+// then the buffers (first call)
+int affine_multi_begin(gar_hip_solver *s, int nrhs, const void *rhs, const void *out, const char *who) {
+  if (int rc = affine_check(s, who))
+    return rc;
+  const std::string w(who);
+  if (nrhs < 1 || !rhs || !out)
+    return fail(GAR_HIP_ERR_ARG, w + ": nrhs must be >= 1 and neither array null");
+  const std::string refusal = s->cur.no_factors(w, "solve");
+  if (!refusal.empty())
+    return fail(GAR_HIP_ERR_ARG, refusal);
+  if (int rc = affine_buffers(s))
+    return rc;
+  if (int rc = affine_multi_buffers(s))
+    return rc;
+  return commit(s); // (a G0 staged through gar_hip_set_init)
+}
+} // namespace
+
+int gar_hip_affine_solve_multi_async(gar_hip_solver *s, int nrhs, const double *rhs_dev, double *out_dev) {
+  GAR_GUARD(s); // (a pipelined sweep: the solver's stream is ordered behind the half streams first)
+  if (int rc = affine_multi_begin(s, nrhs, rhs_dev, out_dev, "gar_hip_affine_solve_multi_async"))
+    return rc;
+  return launch_affine_multi(s, nrhs, rhs_dev, out_dev);
+}
+
+int gar_hip_affine_solve_multi(gar_hip_solver *s, int nrhs, const double *rhs_host, double *out_host) {
+  GAR_GUARD(s);
+  if (int rc = affine_multi_begin(s, nrhs, rhs_host, out_host, "gar_hip_affine_solve_multi"))
+    return rc;
+  // one chunk of columns at a time through a device staging area of the chunk's size (columns are independent: the
+  // results are those of one call on device arrays, bit for bit)
+  const size_t n = (size_t)affine_offsets(s, nullptr), cols = (size_t)s->buf.am_panels * GAR_AM_COLS;
+  const size_t half = ((size_t)s->batch * cols * n + 1) & ~(size_t)1;
+  if (!s->buf.d_am_stage)
+    HIP_TRY(s->buf.d_am_stage.alloc(2 * half + 2));
+  double *in = s->buf.d_am_stage, *res = in + half;
+  for (size_t c0 = 0; c0 < (size_t)nrhs; c0 += cols) {
+    const size_t nc = std::min(cols, (size_t)nrhs - c0);
+    for (size_t b = 0; b < (size_t)s->batch && n > 0; ++b)
+      HIP_TRY(hipMemcpyAsync(in + b * nc * n, rhs_host + (b * (size_t)nrhs + c0) * n, sizeof(double) * nc * n,
+                             hipMemcpyHostToDevice, s->stream));
+    if (int rc = launch_affine_multi(s, (int)nc, in, res))
+      return rc;
+    for (size_t b = 0; b < (size_t)s->batch && n > 0; ++b)
+      HIP_TRY(hipMemcpyAsync(out_host + (b * (size_t)nrhs + c0) * n, res + b * nc * n, sizeof(double) * nc * n,
+                             hipMemcpyDeviceToHost, s->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return failure_epilogue(s, "affine_solve_multi");
 }
 
 int gar_hip_get_status(gar_hip_solver *s, int32_t *out) {

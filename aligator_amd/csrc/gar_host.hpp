@@ -272,6 +272,16 @@ struct LayoutState {
   DevBuf<double> d_adj_rec, d_adj_vec, d_adj_grad;
   DevBuf<int> d_adj_gate;
   size_t adj_grad_lds_bytes = 0;
+  // gar_hip_affine_solve_multi (gar_affine_multi.hpp), all on the first call or none: the work buffers of ONE CHUNK of
+  // am_panels panels of 16 columns per problem -- the panel records of the right-hand sides and of Kff | Yff | Vx, the
+  // initial stage's vx0, g0 and result per (problem, column) -- and the gate words [batch]; sized by the batch, the horizon
+  // and the dimensions, never by nrhs.  The pitches, the three kernels' LDS (bytes).  The synchronous form's device
+  // staging on ITS first call: one chunk of right-hand sides | one chunk of results.
+  DevBuf<double> d_am_rhs, d_am_out, d_am_ivx, d_am_ig0, d_am_ires, d_am_stage;
+  DevBuf<int> d_am_gate;
+  int am_panels = 0, am_nu_max = 0, am_prhs_rec = 0, am_pout_rec = 0, am_ivx_rec = 0, am_ig0_rec = 0, am_init_rec = 0;
+  long long am_prhs_stride = 0, am_pout_stride = 0;
+  size_t am_sweep_lds_bytes = 0, am_roll_lds_bytes = 0, am_init_lds_bytes = 0;
 };
 
 // Layout lifetime, pure host state: what the device records and their host copies describe RIGHT NOW.  Four results are

@@ -980,3 +980,115 @@ int launch_adjoint(gar_hip_solver *s, const double *cot_dev, double *adj_dev, do
   }
   return GAR_HIP_OK;
 }
+
+// ---- many affine terms at once (gar_affine_multi.hpp): panel scatter, the MFMA sweep, the initial stage, the MFMA roll-out ----
+// bytes of the work buffers of one panel of one problem (the header's formula): the two panel records of every stage and
+// the initial stage's three vectors of 16 columns
+size_t affine_multi_panel_bytes(const gar_hip_solver *s, int prhs_rec, int pout_rec, int ivx_rec, int ig0_rec, int init_rec) {
+  return sizeof(double) * ((size_t)(s->horizon + 1) * (size_t)(prhs_rec + pout_rec) +
+                           (size_t)GAR_AM_COLS * (size_t)(ivx_rec + ig0_rec + init_rec));
+}
+// the work buffers of one chunk and the gate words, on the first call after the layout was built (all or none; a failed
+// allocation leaves the solver as it was), and the three kernels' LDS (affine_buffers ran)
+int affine_multi_buffers(gar_hip_solver *s) {
+  if (s->buf.d_am_gate)
+    return GAR_HIP_OK;
+  const int nx_max = s->buf.aff_nx_max, N = s->horizon, C = GAR_AM_COLS;
+  int nu_max = 0, rows = 1, lds = 0, rlds = 0;
+  for (const gar_stage_meta &m : s->meta)
+    nu_max = std::max(nu_max, (int)m.nu);
+  for (const gar_stage_meta &m : s->meta) {
+    rows = std::max(rows, (int)(m.nx + m.nu + m.nx2));
+    lds = std::max(lds, gar::affine_multi_sweep_lds_doubles(nx_max, nu_max, m.nx, m.nu, m.nx2, s->fb_t2, s->vxx_packed));
+    rlds = std::max(rlds, gar::affine_multi_rollout_lds_doubles(nx_max, nu_max, m.nx, m.nu, m.nx2, s->fb_t2, s->vxx_packed));
+  }
+  const int ilds = gar::gar_initial_wave_lds_doubles(s->n0, s->nth0);
+  if ((size_t)std::max(lds, std::max(rlds, ilds)) * sizeof(double) > kCuLdsBytes)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_affine_solve_multi: a stage's blocks and panels need " +
+                                             std::to_string((size_t)std::max(lds, std::max(rlds, ilds)) * sizeof(double)) +
+                                             " B of LDS (> 160 KiB per CU)");
+  const int rec = C * rows, ivx_rec = std::max(2, (s->nx0 + 1) & ~1), ig0_rec = std::max(2, (s->nc0 + 1) & ~1);
+  const int init_rec = std::max(2, (s->n0 + 1) & ~1);
+  // panels per problem in a chunk: enough workgroups for the device at a small batch, at most 1 GiB of work buffers
+  const size_t per_panel = affine_multi_panel_bytes(s, rec, rec, ivx_rec, ig0_rec, init_rec);
+  int panels = std::min(8, std::max(1, (1024 + s->batch - 1) / s->batch));
+  while (panels > 1 && per_panel * (size_t)s->batch * (size_t)panels > ((size_t)1 << 30))
+    --panels;
+  if ((int64_t)s->batch * panels * std::max(N + 1, C) > INT32_MAX)
+    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_affine_solve_multi: batch x (horizon + 1) above 2^31 - 1 workgroups");
+  const size_t bp = (size_t)s->batch * (size_t)panels;
+  const long long stride = (long long)(N + 1) * rec;
+  DevBuf<double> rhs, out, ivx, ig0, ires;
+  DevBuf<int> gate;
+  hipError_t e = rhs.zalloc(bp * (size_t)stride);
+  e = e != hipSuccess ? e : out.zalloc(bp * (size_t)stride);
+  e = e != hipSuccess ? e : ivx.zalloc(bp * C * (size_t)ivx_rec);
+  e = e != hipSuccess ? e : ig0.zalloc(bp * C * (size_t)ig0_rec);
+  e = e != hipSuccess ? e : ires.zalloc(bp * C * (size_t)init_rec);
+  e = e != hipSuccess ? e : gate.zalloc((size_t)s->batch);
+  if (e != hipSuccess) {
+    (void)hipGetLastError(); // (the error is reported here; the next launch check of this solver starts clean)
+    return fail(GAR_HIP_ERR_DEVICE, "gar_hip_affine_solve_multi: " + std::to_string(per_panel * bp + sizeof(int) * (size_t)s->batch) +
+                                        " B of work buffers: " + hipGetErrorString(e));
+  }
+  HIP_TRY(max_lds(gar::gar_affine_sweep_multi, (size_t)lds));
+  HIP_TRY(max_lds(gar::gar_rollout_multi, (size_t)rlds));
+  HIP_TRY(max_lds(gar::gar_affine_multi_initial, (size_t)ilds));
+  s->buf.d_am_rhs = std::move(rhs), s->buf.d_am_out = std::move(out);
+  s->buf.d_am_ivx = std::move(ivx), s->buf.d_am_ig0 = std::move(ig0), s->buf.d_am_ires = std::move(ires);
+  s->buf.d_am_gate = std::move(gate);
+  s->buf.am_panels = panels, s->buf.am_nu_max = nu_max;
+  s->buf.am_prhs_rec = s->buf.am_pout_rec = rec;
+  s->buf.am_ivx_rec = ivx_rec, s->buf.am_ig0_rec = ig0_rec, s->buf.am_init_rec = init_rec;
+  s->buf.am_prhs_stride = s->buf.am_pout_stride = stride;
+  s->buf.am_sweep_lds_bytes = (size_t)lds * sizeof(double);
+  s->buf.am_roll_lds_bytes = (size_t)rlds * sizeof(double);
+  s->buf.am_init_lds_bytes = (size_t)ilds * sizeof(double);
+  return GAR_HIP_OK;
+}
+
+// columns [0, nrhs) of every problem: rhs_dev and out_dev are [batch][nrhs][affine doubles] at DEVICE addresses.  The host
+// loops over chunks of am_panels panels; every kernel of a chunk is ordered behind the previous chunk's on the stream.
+int launch_affine_multi(gar_hip_solver *s, int nrhs, const double *rhs_dev, double *out_dev) {
+  RoctxRange range_("gar::affine_solve_multi");
+  const gar::AffineParams A = make_affine_params(s);
+  if (int rc = ensure_W(s, A))
+    return rc;
+  gar::AffineMultiParams P{};
+  P.meta = s->buf.d_meta;
+  P.U.unx = s->padded ? s->unx : 0, P.U.unu = s->padded ? s->unu : 0;
+  P.U.nc0 = s->user_nc0;
+  P.vec_off = s->buf.d_aff_off;
+  P.vec_stride = affine_offsets(s, nullptr);
+  P.status = status_words(s);
+  P.prob = s->buf.d_prob, P.fac = s->buf.d_fac, P.W = s->buf.d_aff_W;
+  P.prob_stride = s->prob_doubles, P.fac_stride = s->fac_doubles;
+  P.w_rec = s->buf.aff_w_rec, P.horizon = s->horizon, P.nc0 = s->nc0;
+  P.vxx_packed = A.vxx_packed, P.fb_t2 = A.fb_t2;
+  P.nrhs = nrhs;
+  P.rhs = rhs_dev, P.out = out_dev;
+  P.prhs = s->buf.d_am_rhs, P.pout = s->buf.d_am_out;
+  P.ivx = s->buf.d_am_ivx, P.ig0 = s->buf.d_am_ig0, P.ires = s->buf.d_am_ires;
+  P.gate = s->buf.d_am_gate;
+  P.prhs_stride = s->buf.am_prhs_stride, P.pout_stride = s->buf.am_pout_stride;
+  P.prhs_rec = s->buf.am_prhs_rec, P.pout_rec = s->buf.am_pout_rec;
+  P.ivx_rec = s->buf.am_ivx_rec, P.ig0_rec = s->buf.am_ig0_rec, P.init_rec = s->buf.am_init_rec;
+  P.nx_max = s->buf.aff_nx_max, P.nu_max = s->buf.am_nu_max;
+  gar::AffineMultiInit I{};
+  I.G = make_params(s, s->cur.mueq);
+  I.ivx = P.ivx, I.ig0 = P.ig0, I.ires = P.ires, I.gate = P.gate;
+  I.ivx_rec = P.ivx_rec, I.ig0_rec = P.ig0_rec, I.init_rec = P.init_rec;
+  const int C = GAR_AM_COLS, total = (nrhs + C - 1) / C;
+  for (int p0 = 0; p0 < total; p0 += s->buf.am_panels) {
+    P.c0 = p0 * C;
+    P.panels = I.panels = std::min(s->buf.am_panels, total - p0);
+    const unsigned groups = (unsigned)s->batch * (unsigned)P.panels;
+    hipLaunchKernelGGL(gar::gar_affine_multi_scatter, dim3(groups * (unsigned)(s->horizon + 1)), dim3(GAR_AM_THREADS), 0,
+                       s->stream, P);
+    hipLaunchKernelGGL(gar::gar_affine_sweep_multi, dim3(groups), dim3(GAR_AM_THREADS), s->buf.am_sweep_lds_bytes, s->stream, P);
+    hipLaunchKernelGGL(gar::gar_affine_multi_initial, dim3(groups * (unsigned)C), dim3(64), s->buf.am_init_lds_bytes, s->stream, I);
+    hipLaunchKernelGGL(gar::gar_rollout_multi, dim3(groups), dim3(GAR_AM_THREADS), s->buf.am_roll_lds_bytes, s->stream, P);
+    HIP_TRY(hipGetLastError());
+  }
+  return GAR_HIP_OK;
+}

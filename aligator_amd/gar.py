@@ -568,6 +568,25 @@ class BatchedRiccatiSolver:
         records' layout); None before the first adjoint"""
         return self._L.gar_hip_device_adjoints(self._h)
 
+    # ---- many affine terms at once (gar_hip_affine_solve_multi, csrc/gar_affine_multi.hpp) ----------------------------------
+    def affine_solve_multi(self, rhs: np.ndarray) -> np.ndarray:
+        """gar_hip_affine_solve_multi: rhs (batch, nrhs, affine_doubles) holds, for every problem, nrhs sets of affine terms
+        (q_t | r_t | f_t per stage, then g0).  -> the LQ solutions for the resident matrices and those terms, same shape
+        (x_t | u_t | lbd_{t+1} per stage, then lbd0).  Needs a backward, no forward; nothing of the primal is written."""
+        rhs = np.ascontiguousarray(rhs, dtype=np.float64)
+        n = self.affine_doubles
+        if rhs.ndim != 3 or rhs.shape[0] != self.batch or rhs.shape[2] != n:
+            raise ValueError(f"rhs of shape {rhs.shape}, expected (batch = {self.batch}, nrhs, affine_doubles = {n})")
+        out = np.zeros(rhs.shape)
+        self._check(self._L.gar_hip_affine_solve_multi(self._h, int(rhs.shape[1]), _ptr(rhs), _ptr(out)))
+        return out
+
+    def affine_solve_multi_async(self, rhs_ptr: int, nrhs: int, out_ptr: int):
+        """gar_hip_affine_solve_multi_async: device addresses of (batch, nrhs, affine_doubles) arrays; enqueued, not
+        waited for"""
+        self._check(self._L.gar_hip_affine_solve_multi_async(self._h, int(nrhs), C.c_void_p(rhs_ptr or None),
+                                                             C.c_void_p(out_ptr or None)))
+
     def unpack_gradient(self, buf: np.ndarray) -> LqrProblem:
         """one gradient record of adjoint() as an LqrProblem whose blocks are the gradients of the same-named blocks"""
         return self.unpack(np.asarray(buf, dtype=np.float64).reshape(-1))

@@ -12,7 +12,9 @@ One solver, one batch: the layer does not resize it.  The gradient with respect 
 backward differentiates what the solver HOLDS: it must run before the next forward on the same solver (a later forward makes
 the earlier graph's backward raise); whoever drives the solver directly between the two (upload, backward, refine)
 is on their own.  The layer also owns the solver's stream: after a direct solver.set_stream, call forget_stream(solver).
-On the emulator build of the library device pointers are host pointers: the same layer runs on CPU tensors there."""
+On the emulator build of the library device pointers are host pointers: the same layer runs on CPU tensors there.
+lq_affine_solve_multi(solver, rhs) solves the batch the solver holds for many sets of affine terms at once, on the same
+stream discipline (no autograd: it is the adjoint solve itself, for several cotangents)."""
 import torch
 
 from .gar import BatchedRiccatiSolver
@@ -85,6 +87,22 @@ class LqSolve(torch.autograd.Function):
         solver.adjoint_async(cot.data_ptr(), 0, grad.data_ptr())
         _end(token, (cot, grad))
         return grad, None, None
+
+
+def lq_affine_solve_multi(solver: BatchedRiccatiSolver, rhs: torch.Tensor) -> torch.Tensor:
+    """rhs (batch, nrhs, affine_doubles), float64 on the solver's device: for every problem, nrhs sets of affine terms (q_t
+    | r_t | f_t per stage, then g0).  -> the LQ solutions for the matrices the solver holds and those terms, same shape
+    (affine_solve_multi_async, csrc/gar_affine_multi.hpp).  Enqueued on torch's current stream, not waited for; not
+    differentiable (no graph is recorded).  The solver needs a backward whose matrices are still current."""
+    if rhs.dtype != torch.float64 or rhs.dim() != 3 or rhs.shape[0] != solver.batch or rhs.shape[2] != solver.affine_doubles:
+        raise ValueError(f"rhs must be float64 of shape ({solver.batch}, nrhs, {solver.affine_doubles}), "
+                         f"got {rhs.dtype} {tuple(rhs.shape)}")
+    src = rhs.detach().contiguous()
+    out = torch.empty_like(src)
+    token = _begin(solver, src)
+    solver.affine_solve_multi_async(src.data_ptr(), int(src.shape[1]), out.data_ptr())
+    _end(token, (src, out))
+    return out
 
 
 class LqLayer(torch.nn.Module):

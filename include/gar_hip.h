@@ -461,6 +461,38 @@ int gar_hip_adjoint(gar_hip_solver *s, const double *cot_host, double *adj_host 
  * the first adjoint and on a multi-device handle */
 const double *gar_hip_device_adjoints(gar_hip_solver *s);
 
+/* ---- the resident batch solved for MANY affine terms at once (csrc/gar_affine_multi.hpp) -------------------------------------
+ * For every problem b and every column j < nrhs: the LQ solution for the resident MATRICES and the affine terms
+ * (q, r, f, g0) := rhs[b][j] -- K d = -g in the notation above; for one column, what gar_hip_adjoint_async(cot, adj_out,
+ * NULL) computes.  The columns of one problem ride side by side as panels of 16 through the vector half of the Riccati
+ * recursion and the roll-out on f64 MFMA tiles: a stage's matrices (fb, Vxx', W, B) are fetched once per 16 columns.
+ *   rhs, out   [batch][nrhs][gar_hip_affine_doubles], the caller's dimensions.  rhs: q_t | r_t | f_t per stage, then g0 (a
+ *              terminal knot's f slot, where the layout has one, is ignored).  out: x_t | u_t | lbd_{t+1} per stage, then
+ *              lbd0 (a terminal f slot: zero).
+ *   gar_hip_affine_solve_multi_async  device addresses; enqueued on the solver's stream (behind the half streams of a
+ *              pipelined sweep), no host wait.
+ *   gar_hip_affine_solve_multi        the same from and to HOST arrays, a chunk of columns at a time through a device
+ *              staging area (allocated by its first call); synchronous, returns like gar_hip_adjoint (GAR_HIP_ERR_FACTOR
+ *              when a status word is non-zero).
+ * A problem whose status word is non-zero gets exact zeros in all its columns.
+ * What keeps its bits: EVERYTHING of the primal -- knots, factor records, gains, solution records, status words, the KKT
+ * buffers, W (formed first if it is stale) and the host copies; the call is no transition of the run state.  It shares no
+ * buffer with the refinement or the adjoint: a refinement step or an adjoint before or after gives the bits it gives
+ * without it.
+ * State (otherwise GAR_HIP_ERR_ARG naming the reason, nothing launched): nrhs >= 1, neither array null, a backward whose
+ * matrix blocks are still current (gar_hip_backward_affine's rules).  No forward is needed: the primal solution is not
+ * read.  Served: exactly who gar_hip_backward_affine serves; everyone else answers GAR_HIP_ERR_UNSUPPORTED with nothing
+ * launched and nothing touched.
+ * Work buffers: ONE CHUNK of P panels per problem, allocated by the first call (gar_hip_debug_alloc_count rises then and
+ * not again, whatever nrhs later calls bring); the host loops over chunks of 16 P columns.  With (nx, nu, nx2) the largest
+ * device dimensions and n0 = nx0 + nc0, their size is
+ *   batch * P * 8 * [ (horizon + 1) * 2 * 16 * (nx + nu + nx2) + 16 * (even(nx0) + even(nc0) + even(n0)) ]  bytes
+ * plus batch gate words; P = min(8, ceil(1024 / batch)), lowered (not below 1) until that is at most 1 GiB.  At (36, 12),
+ * horizon 256, batch 4 096: P = 1 and 22.7 GB.  A failed allocation answers GAR_HIP_ERR_DEVICE (the library has no code
+ * of its own for it) with the byte count; nothing is kept and the solver stays usable. */
+int gar_hip_affine_solve_multi_async(gar_hip_solver *s, int nrhs, const double *rhs_dev, double *out_dev);
+int gar_hip_affine_solve_multi(gar_hip_solver *s, int nrhs, const double *rhs_host, double *out_host);
+
 /* Diagnostics of the last backward (specialised kernel families; no reference counterpart): the
  * register LDL^T of Rhat is what Bunch-Kaufman does whenever its first test |a_kk| >= alpha*colmax
  * holds at every column (bunchkaufman.hpp:61); out[0] = stages (summed over the batch) where it did
