@@ -1,7 +1,10 @@
 // gar_hip.cpp -- C-ABI implementation (include/gar_hip.h) over the HIP kernels.
 // Host C++ only packs per-stage blocks into the contiguous device records,
 // launches kernels on a HIP stream and copies results back; all arithmetic of
-// the Riccati path runs in the kernels (gar_generic.hpp, gar_mfma.hpp).
+// the Riccati path runs in the kernels (gar_generic.hpp, gar_mfma.hpp).  The unit's host code is split over headers
+// included in place: gar_host.hpp (what a solver is made of), gar_select.hpp (kernel families), gar_launch.hpp (the sweeps'
+// launches), gar_resident.hpp (the services on a resident batch), gar_multi.hpp, gar_entry_io.hpp; the extern "C" entry
+// points are here.
 #include "../../include/gar_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -717,6 +720,7 @@ enum { kBehindStream = 1, kBehindHost = 2 };
 int settle_gains_readback(gar_hip_solver *s, int behind);
 
 #include "gar_launch.hpp"
+#include "gar_resident.hpp"
 
 int allocate(gar_hip_solver *s) {
   const size_t B = (size_t)s->batch;
@@ -1595,7 +1599,7 @@ int gar_hip_forward(gar_hip_solver *s, const double *theta) {
   return GAR_HIP_OK;
 }
 
-// ---- lqrComputeKktError for the whole batch, on the device (gar_kkt.hpp; launch_kkt in gar_launch.hpp) -------------
+// ---- lqrComputeKktError for the whole batch, on the device (gar_kkt.hpp; launch_kkt in gar_resident.hpp) -----------
 namespace {
 int kkt_check(const gar_hip_solver *s, const void *theta) {
   if (!s)
@@ -1631,8 +1635,8 @@ int gar_hip_kkt_error(gar_hip_solver *s, double mueq, const double *theta_host, 
   }
   if (int rc = launch_kkt(s, mueq, th))
     return rc;
-  int rc = d2h(s, out3, s->buf.d_kkt_err, (int64_t)s->batch * 3);
-  rc |= d2h(s, stage4, s->buf.d_kkt_stage, (int64_t)s->batch * (s->horizon + 1) * 4);
+  int rc = d2h(s, out3, s->buf.kkt.err, (int64_t)s->batch * 3);
+  rc |= d2h(s, stage4, s->buf.kkt.stage, (int64_t)s->batch * (s->horizon + 1) * 4);
   if (rc)
     return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1641,40 +1645,34 @@ int gar_hip_kkt_error(gar_hip_solver *s, double mueq, const double *theta_host, 
 
 const double *gar_hip_device_kkt_errors(gar_hip_solver *s) {
   pipe_autojoin(s);
-  return s && !s->multi ? s->buf.d_kkt_err.get() : nullptr;
+  return s && !s->multi ? s->buf.kkt.err.get() : nullptr;
 }
 const double *gar_hip_device_kkt_stage_errors(gar_hip_solver *s) {
   pipe_autojoin(s);
-  return s && !s->multi ? s->buf.d_kkt_stage.get() : nullptr;
+  return s && !s->multi ? s->buf.kkt.stage.get() : nullptr;
 }
 
-// ---- re-solve for new affine terms from the stored factorisation (gar_affine.hpp; launches in gar_launch.hpp) ---------
+// ---- the services on a resident batch (gar_resident.hpp: work areas, launches and resident_begin, the prologue) -------
+// re-solve for new affine terms from the stored factorisation (gar_affine.hpp)
 int64_t gar_hip_affine_doubles(const gar_hip_solver *s) { return s && !s->user_dims5.empty() ? affine_offsets(s, nullptr) : 0; }
 
 int gar_hip_upload_affine_device(gar_hip_solver *s, int b0, int nb, const double *affine_dev) {
   GAR_GUARD(s);
-  if (int rc = affine_check(s, "gar_hip_upload_affine_device"))
-    return rc;
-  if (!affine_dev || b0 < 0 || nb < 0 || b0 + nb > s->batch)
-    return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_affine_device: bad argument");
-  if (int rc = affine_buffers(s))
+  if (int rc = resident_begin(s, "gar_hip_upload_affine_device", bad_range(s, affine_dev, b0, nb), nullptr, 0, {ensure_affine}))
     return rc;
   return launch_affine_scatter(s, b0, nb, affine_dev);
 }
 
 int gar_hip_upload_affine(gar_hip_solver *s, int b0, int nb, const double *affine_host) {
   GAR_GUARD(s);
-  if (int rc = affine_check(s, "gar_hip_upload_affine"))
-    return rc;
-  if (!affine_host || b0 < 0 || nb < 0 || b0 + nb > s->batch)
-    return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_affine: bad argument");
-  if (int rc = affine_buffers(s))
+  if (int rc = resident_begin(s, "gar_hip_upload_affine", bad_range(s, affine_host, b0, nb), nullptr, 0, {ensure_affine}))
     return rc;
   const size_t n = (size_t)affine_offsets(s, nullptr);
   if (n == 0 || nb == 0)
     return GAR_HIP_OK;
-  if (!s->buf.d_aff_in)
-    HIP_TRY(s->buf.d_aff_in.alloc(n * (size_t)s->batch));
+  gar::AffineArea &a = s->buf.aff;
+  if (!a.staging)
+    HIP_TRY(a.staging.alloc(n * (size_t)s->batch));
   if (int rc = commit(s)) // (the pinned area is free once its staged blocks are on their way)
     return rc;
   // through the pinned staging area where there is one (a problem's record is longer than its affine vector)
@@ -1684,8 +1682,8 @@ int gar_hip_upload_affine(gar_hip_solver *s, int b0, int nb, const double *affin
     std::memcpy(s->buf.h_prob.get(), affine_host, sizeof(double) * n * (size_t)nb);
     from = s->buf.h_prob;
   }
-  HIP_TRY(hipMemcpyAsync(s->buf.d_aff_in.get(), from, sizeof(double) * n * (size_t)nb, hipMemcpyHostToDevice, s->stream));
-  if (int rc = launch_affine_scatter(s, b0, nb, s->buf.d_aff_in))
+  HIP_TRY(hipMemcpyAsync(a.staging.get(), from, sizeof(double) * n * (size_t)nb, hipMemcpyHostToDevice, s->stream));
+  if (int rc = launch_affine_scatter(s, b0, nb, a.staging))
     return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
   return GAR_HIP_OK;
@@ -1693,12 +1691,7 @@ int gar_hip_upload_affine(gar_hip_solver *s, int b0, int nb, const double *affin
 
 int gar_hip_backward_affine_async(gar_hip_solver *s) {
   GAR_GUARD(s); // (a pipelined sweep: the solver's stream is ordered behind the half streams first)
-  if (int rc = affine_check(s, "gar_hip_backward_affine"))
-    return rc;
-  const std::string refusal = s->cur.no_factors("gar_hip_backward_affine", "re-solve");
-  if (!refusal.empty())
-    return fail(GAR_HIP_ERR_ARG, refusal);
-  if (int rc = affine_buffers(s))
+  if (int rc = resident_begin(s, "gar_hip_backward_affine", nullptr, "re-solve", 0, {ensure_affine}))
     return rc;
   return launch_backward_affine(s);
 }
@@ -1710,28 +1703,11 @@ int gar_hip_backward_affine(gar_hip_solver *s) {
   return failure_epilogue(s, "backward_affine");
 }
 
-// ---- iterative refinement from the stored factorisation (gar_refine.hpp; launches in gar_launch.hpp) -------------------
+// iterative refinement from the stored factorisation (gar_refine.hpp)
 namespace {
-// who is served and the state a step needs; then the buffers (first call) and everything a step must be ordered behind
 int refine_begin(gar_hip_solver *s, int steps, double threshold, const char *who) {
-  if (int rc = affine_check(s, who))
-    return rc;
-  const std::string w(who);
-  if (steps < 0 || threshold != threshold)
-    return fail(GAR_HIP_ERR_ARG, w + ": the step count must be >= 0 and the threshold not NaN");
-  const std::string refusal = s->cur.no_factors(w, "refine");
-  if (!refusal.empty())
-    return fail(GAR_HIP_ERR_ARG, refusal);
-  if (!s->cur.rolled_out)
-    return fail(GAR_HIP_ERR_ARG, w + ": no forward since the last backward (there is no solution to refine)");
-  if (int rc = affine_buffers(s))
-    return rc;
-  if (int rc = kkt_buffers(s))
-    return rc;
-  if (int rc = refine_buffers(s))
-    return rc;
-  s->cur.solution_superseded(); // (the host copy gar_hip_backward_blocks left is the unrefined solution)
-  return commit(s);     // (a g0 staged through gar_hip_set_init)
+  const char *bad = steps < 0 || threshold != threshold ? "the step count must be >= 0 and the threshold not NaN" : nullptr;
+  return resident_begin(s, who, bad, "refine", kNeedsSolution | kSupersedesSolution | kCommits, {ensure_refine, ensure_kkt});
 }
 } // namespace
 
@@ -1759,7 +1735,7 @@ int gar_hip_refine(gar_hip_solver *s, int max_steps, double threshold, int32_t o
   for (;;) {
     if (int rc = launch_refine_residual(s, threshold))
       return rc;
-    HIP_TRY(hipMemcpyAsync(gate.data(), s->buf.d_ref_gate.get(), sizeof(int) * gate.size(), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(gate.data(), s->buf.ref.gate.get(), sizeof(int) * gate.size(), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     remaining = 0;
     for (int v : gate)
@@ -1777,16 +1753,11 @@ int gar_hip_refine(gar_hip_solver *s, int max_steps, double threshold, int32_t o
   return failure_epilogue(s, "refine");
 }
 
-// ---- gradients of a resident batch (gar_adjoint.hpp; launches in gar_launch.hpp) -----------------------------------------
+// gradients of a resident batch (gar_adjoint.hpp)
 int gar_hip_upload_packed_user_device(gar_hip_solver *s, int b0, int nb, const double *packed_user_dev) {
   GAR_GUARD(s);
-  if (int rc = affine_check(s, "gar_hip_upload_packed_user_device"))
-    return rc;
-  if (!packed_user_dev || b0 < 0 || nb < 0 || b0 + nb > s->batch)
-    return fail(GAR_HIP_ERR_ARG, "gar_hip_upload_packed_user_device: bad argument");
-  if (int rc = user_layout_buffers(s))
-    return rc;
-  if (int rc = commit(s)) // staged host data first, then the device copy wins
+  if (int rc = resident_begin(s, "gar_hip_upload_packed_user_device", bad_range(s, packed_user_dev, b0, nb), nullptr,
+                              kCommits, {ensure_user_layout})) // staged host data first, then the device copy wins
     return rc;
   s->cur.matrices_changed("gar_hip_upload_packed_user_device");
   return launch_user_upload(s, b0, nb, packed_user_dev);
@@ -1794,39 +1765,18 @@ int gar_hip_upload_packed_user_device(gar_hip_solver *s, int b0, int nb, const d
 
 int gar_hip_solution_vectors_device(gar_hip_solver *s, int b0, int nb, double *out_dev) {
   GAR_GUARD(s); // (a pipelined sweep: the solver's stream is ordered behind the half streams first)
-  if (int rc = affine_check(s, "gar_hip_solution_vectors_device"))
-    return rc;
-  if (!out_dev || b0 < 0 || nb < 0 || b0 + nb > s->batch)
-    return fail(GAR_HIP_ERR_ARG, "gar_hip_solution_vectors_device: bad argument");
-  if (int rc = affine_buffers(s))
-    return rc;
-  if (int rc = user_layout_buffers(s))
+  if (int rc = resident_begin(s, "gar_hip_solution_vectors_device", bad_range(s, out_dev, b0, nb), nullptr, 0,
+                              {ensure_affine, ensure_user_layout}))
     return rc;
   return launch_solution_gather(s, b0, nb, s->buf.d_sol, out_dev);
 }
 
 namespace {
-// who is served and the state an adjoint needs; then the buffers (first call)
 int adjoint_begin(gar_hip_solver *s, const void *cot, const void *grad, const char *who) {
-  if (int rc = affine_check(s, who))
-    return rc;
-  const std::string w(who);
-  if (!cot)
-    return fail(GAR_HIP_ERR_ARG, w + ": null cotangent");
-  if (reinterpret_cast<uintptr_t>(grad) & 15)
-    return fail(GAR_HIP_ERR_ARG, w + ": the gradient records must start on a 16-byte boundary");
-  const std::string refusal = s->cur.no_factors(w, "differentiate");
-  if (!refusal.empty())
-    return fail(GAR_HIP_ERR_ARG, refusal);
-  if (!s->cur.rolled_out)
-    return fail(GAR_HIP_ERR_ARG, w + ": no forward since the last backward (there is no solution to differentiate)");
-  if (int rc = affine_buffers(s))
-    return rc;
-  if (int rc = refine_buffers(s))
-    return rc;
-  if (int rc = adjoint_buffers(s))
-    return rc;
-  return commit(s); // (a g0 staged through gar_hip_set_init)
+  const char *bad = !cot ? "null cotangent" : nullptr;
+  if (!bad && (reinterpret_cast<uintptr_t>(grad) & 15))
+    bad = "the gradient records must start on a 16-byte boundary";
+  return resident_begin(s, who, bad, "differentiate", kNeedsSolution | kCommits, {ensure_adjoint});
 }
 } // namespace
 
@@ -1843,17 +1793,18 @@ int gar_hip_adjoint(gar_hip_solver *s, const double *cot_host, double *adj_host,
     return rc;
   const size_t n = (size_t)affine_offsets(s, nullptr) * (size_t)s->batch;
   const size_t ng = (size_t)caller_layout(s).prob_doubles * (size_t)s->batch;
-  if (!s->buf.d_adj_vec)
-    HIP_TRY(s->buf.d_adj_vec.alloc(2 * n + 2));
-  if (grad_host && !s->buf.d_adj_grad)
-    HIP_TRY(s->buf.d_adj_grad.alloc(ng));
-  double *cot = s->buf.d_adj_vec, *adj = cot + n;
+  gar::AdjointArea &a = s->buf.adj;
+  if (!a.staging)
+    HIP_TRY(a.staging.alloc(2 * n + 2));
+  if (grad_host && !a.grad)
+    HIP_TRY(a.grad.alloc(ng));
+  double *cot = a.staging, *adj = cot + n;
   HIP_TRY(hipMemcpyAsync(cot, cot_host, sizeof(double) * n, hipMemcpyHostToDevice, s->stream));
-  if (int rc = launch_adjoint(s, cot, adj_host ? adj : nullptr, grad_host ? s->buf.d_adj_grad.get() : nullptr))
+  if (int rc = launch_adjoint(s, cot, adj_host ? adj : nullptr, grad_host ? a.grad.get() : nullptr))
     return rc;
   if (int rc = d2h(s, adj_host, adj, (int64_t)n))
     return rc;
-  if (int rc = d2h(s, grad_host, s->buf.d_adj_grad, (int64_t)ng))
+  if (int rc = d2h(s, grad_host, a.grad, (int64_t)ng))
     return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
   return failure_epilogue(s, "adjoint");
@@ -1861,27 +1812,15 @@ int gar_hip_adjoint(gar_hip_solver *s, const double *cot_host, double *adj_host,
 
 const double *gar_hip_device_adjoints(gar_hip_solver *s) {
   pipe_autojoin(s);
-  return s && !s->multi ? s->buf.d_adj_rec.get() : nullptr;
+  return s && !s->multi ? s->buf.adj.rec.get() : nullptr;
 }
 
-// ---- many affine terms at once (gar_affine_multi.hpp; launches in gar_launch.hpp) --------------------------------------------
+// many affine terms at once (gar_affine_multi.hpp): gar_hip_backward_affine's state -- no forward, the primal solution is
+// not read
 namespace {
-// who is served and the state the solve needs (gar_hip_backward_affine's; no forward: the primal solution is not read);
-// then the buffers (first call)
 int affine_multi_begin(gar_hip_solver *s, int nrhs, const void *rhs, const void *out, const char *who) {
-  if (int rc = affine_check(s, who))
-    return rc;
-  const std::string w(who);
-  if (nrhs < 1 || !rhs || !out)
-    return fail(GAR_HIP_ERR_ARG, w + ": nrhs must be >= 1 and neither array null");
-  const std::string refusal = s->cur.no_factors(w, "solve");
-  if (!refusal.empty())
-    return fail(GAR_HIP_ERR_ARG, refusal);
-  if (int rc = affine_buffers(s))
-    return rc;
-  if (int rc = affine_multi_buffers(s))
-    return rc;
-  return commit(s); // (a G0 staged through gar_hip_set_init)
+  const char *bad = nrhs < 1 || !rhs || !out ? "nrhs must be >= 1 and neither array null" : nullptr;
+  return resident_begin(s, who, bad, "solve", kCommits, {ensure_affine_multi});
 }
 } // namespace
 
@@ -1898,11 +1837,11 @@ int gar_hip_affine_solve_multi(gar_hip_solver *s, int nrhs, const double *rhs_ho
     return rc;
   // one chunk of columns at a time through a device staging area of the chunk's size (columns are independent: the
   // results are those of one call on device arrays, bit for bit)
-  const size_t n = (size_t)affine_offsets(s, nullptr), cols = (size_t)s->buf.am_panels * GAR_AM_COLS;
+  const size_t n = (size_t)affine_offsets(s, nullptr), cols = (size_t)s->buf.am.panels * GAR_AM_COLS;
   const size_t half = ((size_t)s->batch * cols * n + 1) & ~(size_t)1;
-  if (!s->buf.d_am_stage)
-    HIP_TRY(s->buf.d_am_stage.alloc(2 * half + 2));
-  double *in = s->buf.d_am_stage, *res = in + half;
+  if (!s->buf.am.staging)
+    HIP_TRY(s->buf.am.staging.alloc(2 * half + 2));
+  double *in = s->buf.am.staging, *res = in + half;
   for (size_t c0 = 0; c0 < (size_t)nrhs; c0 += cols) {
     const size_t nc = std::min(cols, (size_t)nrhs - c0);
     for (size_t b = 0; b < (size_t)s->batch && n > 0; ++b)

@@ -1,8 +1,9 @@
 // gar_host.hpp -- what the solver handle (gar_hip.cpp: gar_hip_solver) is made of, apart from its settings: the record
 // layout of one problem (HostLayout: build_layout fills it; the caller-facing and the scratch layouts of a solver are
 // bare ones), the kernel family bound to it (KernelBinding: select_kernel resets it by value and the bind_* functions of
-// gar_select.hpp fill it) and the run state, grouped by lifetime (LayoutState, PipeState, LazyState) and held in the
-// four move-only owners below, beside the one record of what is current (Current).  Included by gar_hip.cpp behind
+// gar_select.hpp fill it) and the run state, grouped by lifetime (LayoutState -- with one work-area record per service on a
+// resident batch, KktArea ... AffineMultiArea -- PipeState, LazyState) and held in the four move-only owners below, beside
+// the one record of what is current (Current).  Included by gar_hip.cpp behind
 // <hip/hip_runtime.h>, its standard headers (<atomic>, <cstdlib>, <cstring>, <map>, <mutex>, <string>, <utility>,
 // <vector>: none is included here) and the kernel headers; internal linkage, like the rest of that unit's host code.
 // Ahead of them: gar_option and its two predicates, which need nothing of a solver.
@@ -210,8 +211,55 @@ struct KernelBinding {
   bool sf_fb_t2 = false, sf_vxx_packed = false, sf_qr_packed = false;
 };
 
+// ---- work areas of the services on a resident batch ---------------------------------------------------------------
+// One record per service: its device buffers, their record pitches and its kernels' LDS (bytes).  gar_resident.hpp's
+// ensure_* build one as a local value and move-assign it whole on the service's first call after the layout was built: a
+// work area is there with all its members or not at all (built()), and a failed allocation leaves the solver as it was.
+// The one member that comes later is the staging buffer of the service's synchronous form, on ITS first call.
+struct KktArea { // gar_hip_kkt_error (gar_kkt.hpp)
+  DevBuf<double> stage, err; // the stage norms [batch][horizon + 1][4], the triples [batch][3]
+  size_t lds_bytes = 0;      // one workgroup of gar_kkt_stage_residuals
+  bool built() const { return stage; }
+};
+struct AffineArea { // gar_hip_backward_affine (gar_affine.hpp)
+  DevBuf<double> W;       // Rhat^-1 [batch][horizon + 1][w_rec] (Current::W_valid)
+  DevBuf<int> ok;         // the "re-solved" flags [batch]
+  DevBuf<long long> off;  // the offsets of the caller's affine vector [horizon + 2]
+  DevBuf<double> staging; // gar_hip_upload_affine: batch vectors
+  int w_rec = 0, nx_max = 0;
+  size_t sweep_lds_bytes = 0, prep_lds_bytes = 0;
+  bool built() const { return off; }
+};
+struct RefineArea { // gar_hip_refine (gar_refine.hpp)
+  DevBuf<double> rhs, out, init; // the right-hand side (the residual vectors), the correction's ff~ / vx~, its initial stage's result
+  DevBuf<int> gate;              // the gate words [batch]
+  int rhs_rec = 0, out_rec = 0, init_rec = 0;
+  long long rhs_stride = 0, out_stride = 0;
+  size_t sweep_lds_bytes = 0, roll_lds_bytes = 0, init_lds_bytes = 0;
+  bool built() const { return gate; }
+};
+struct AdjointArea { // gar_hip_adjoint (gar_adjoint.hpp); right-hand side, ff~ / vx~ and the initial stage's result: the refinement's
+  DevBuf<double> rec;           // the adjoint records [batch][sol_doubles]
+  DevBuf<int> gate;             // the gate words [batch]
+  DevBuf<double> staging, grad; // gar_hip_adjoint: cotangents | adjoints; the gradient records on the first call that asks for them
+  size_t grad_lds_bytes = 0;
+  bool built() const { return gate; }
+};
+// gar_hip_affine_solve_multi (gar_affine_multi.hpp): the work buffers of ONE CHUNK of `panels` panels of 16 columns per
+// problem, sized by the batch, the horizon and the dimensions, never by nrhs
+struct AffineMultiArea {
+  DevBuf<double> rhs, out;      // the panel records of the right-hand sides and of Kff | Yff | Vx
+  DevBuf<double> ivx, ig0, ires; // the initial stage's vx0, g0 and result per (problem, column)
+  DevBuf<int> gate;             // the gate words [batch]
+  DevBuf<double> staging;       // gar_hip_affine_solve_multi: one chunk of right-hand sides | one chunk of results
+  int panels = 0, nu_max = 0, prhs_rec = 0, pout_rec = 0, ivx_rec = 0, ig0_rec = 0, init_rec = 0;
+  long long prhs_stride = 0, pout_stride = 0;
+  size_t sweep_lds_bytes = 0, roll_lds_bytes = 0, init_lds_bytes = 0;
+  bool built() const { return gate; }
+};
+
 // ---- run state, by lifetime ---------------------------------------------------------------------------------------
-// Layout lifetime: built by allocate() or, member by member, on an entry point's first use; dropped as one value
+// Layout lifetime: built by allocate() or, member by member (a work area: whole), on an entry point's first use; dropped as one value
 // (`s->buf = {}`, behind a stream synchronisation) when gar_hip_cycle_append changes the dimensions, and with the solver.
 struct LayoutState {
   DevBuf<gar_stage_meta> d_meta;
@@ -243,45 +291,15 @@ struct LayoutState {
   DevBuf<long long> d_gain_off;
   DevBuf<double> d_gains;
   PinnedBuf<double> h_results;
-  // gar_hip_kkt_error (gar_kkt.hpp): the stage norms [batch][horizon + 1][4] and the triples [batch][3], both on
-  // the first call or neither; the LDS one workgroup of gar_kkt_stage_residuals asks for (bytes)
-  DevBuf<double> d_kkt_stage, d_kkt_err;
-  size_t kkt_lds_bytes = 0;
-  // gar_hip_backward_affine (gar_affine.hpp), all on the first call or none: W = Rhat^-1 [batch][horizon + 1][aff_w_rec],
-  // the "re-solved" flags [batch], the offsets of the caller's affine vector [horizon + 2]; the host upload's device
-  // staging (batch vectors) on ITS first call
-  DevBuf<double> d_aff_W, d_aff_in;
-  DevBuf<int> d_aff_ok;
-  DevBuf<long long> d_aff_off;
-  int aff_w_rec = 0, aff_nx_max = 0;
-  size_t aff_lds_bytes = 0, aff_prep_lds_bytes = 0;
-  // gar_hip_refine (gar_refine.hpp), all on the first call or none: the right-hand side (the residual vectors), the
-  // correction's ff~ / vx~, its initial stage's result, the gate words [batch]; the records' pitches and the three
-  // kernels' LDS (bytes)
-  DevBuf<double> d_ref_rhs, d_ref_out, d_ref_init;
-  DevBuf<int> d_ref_gate;
-  int ref_rhs_rec = 0, ref_out_rec = 0, ref_init_rec = 0;
-  long long ref_rhs_stride = 0, ref_out_stride = 0;
-  size_t ref_sweep_lds_bytes = 0, ref_roll_lds_bytes = 0, ref_init_lds_bytes = 0;
-  // gar_hip_adjoint (gar_adjoint.hpp).  A padded solver's caller-side knot offsets [horizon + 1], on the first call that
-  // speaks the caller's packed layout on the device (the upload scatter, the gradient kernel).  The adjoint records
-  // [batch][sol_doubles] and the gate words [batch], both on the first adjoint or neither; the gradient kernel's LDS
-  // (bytes).  The synchronous form's device staging on ITS first call: cotangents | adjoints, and the gradient records
-  // on the first call that asks for them.  (Right-hand side, ff~ / vx~ and the initial stage's result: the refinement's.)
-  DevBuf<long long> d_adj_uoff;
-  DevBuf<double> d_adj_rec, d_adj_vec, d_adj_grad;
-  DevBuf<int> d_adj_gate;
-  size_t adj_grad_lds_bytes = 0;
-  // gar_hip_affine_solve_multi (gar_affine_multi.hpp), all on the first call or none: the work buffers of ONE CHUNK of
-  // am_panels panels of 16 columns per problem -- the panel records of the right-hand sides and of Kff | Yff | Vx, the
-  // initial stage's vx0, g0 and result per (problem, column) -- and the gate words [batch]; sized by the batch, the horizon
-  // and the dimensions, never by nrhs.  The pitches, the three kernels' LDS (bytes).  The synchronous form's device
-  // staging on ITS first call: one chunk of right-hand sides | one chunk of results.
-  DevBuf<double> d_am_rhs, d_am_out, d_am_ivx, d_am_ig0, d_am_ires, d_am_stage;
-  DevBuf<int> d_am_gate;
-  int am_panels = 0, am_nu_max = 0, am_prhs_rec = 0, am_pout_rec = 0, am_ivx_rec = 0, am_ig0_rec = 0, am_init_rec = 0;
-  long long am_prhs_stride = 0, am_pout_stride = 0;
-  size_t am_sweep_lds_bytes = 0, am_roll_lds_bytes = 0, am_init_lds_bytes = 0;
+  // the caller-side knot offsets [horizon + 1] of a padded solver, on the first call that speaks the caller's packed layout on
+  // the device (the upload scatter, the gradient kernel)
+  DevBuf<long long> d_user_off;
+  // the services on the resident batch, one work area each (above; gar_resident.hpp builds them on first use)
+  KktArea kkt;
+  AffineArea aff;
+  RefineArea ref;
+  AdjointArea adj;
+  AffineMultiArea am;
 };
 
 // Layout lifetime, pure host state: what the device records and their host copies describe RIGHT NOW.  Four results are
@@ -295,7 +313,7 @@ struct Current {
   Factors factors = kNone;           // what gar_hip_backward_affine / gar_hip_refine may re-solve from
   const char *stale_cause = nullptr; // kStale: the entry point that changed matrix blocks
   double mueq = 0.0;                 // of the last backward (the fold, the re-solve's initial stage, the refinement)
-  bool W_valid = false;              // d_aff_W belongs to the factor records
+  bool W_valid = false;              // AffineArea::W belongs to the factor records
   bool expanded = false;             // folded solvers: the caller-visible factor records are formed ...
   bool know_coupled = false;        // ... and LayoutState::h_coupled holds which problems the generic kernels took
   bool rolled_out = false;           // a roll-out of this factorisation is enqueued: there is a solution to refine

@@ -1,5 +1,6 @@
 // gar_launch.hpp -- kernel parameter blocks (one make_* each) and launches of the sweeps, one function per kernel family:
-// launch_backward, launch_forward, the pipelined schedule (gar_pipeline.hpp), launch_condensed.
+// launch_backward, launch_forward, the pipelined schedule (gar_pipeline.hpp), launch_condensed.  (What a batch that stays in
+// HBM is asked besides its sweeps -- KKT residuals, re-solve, refinement, adjoint, many affine terms: gar_resident.hpp.)
 // Part of the ONE translation unit gar_hip.cpp (included in place: it uses the solver struct and the helpers defined
 // above its include line); split out for readability only.
 #pragma once
@@ -551,544 +552,5 @@ int d2h(gar_hip_solver *s, double *dst, const double *src, int64_t n) {
   if (!dst || n <= 0)
     return GAR_HIP_OK;
   HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s->stream));
-  return GAR_HIP_OK;
-}
-
-// ---- the KKT residuals of the whole batch (gar_kkt.hpp): one launch sequence for every solver family ------------------
-gar::KktParams make_kkt_params(gar_hip_solver *s, double mueq, const double *theta_dev) {
-  gar::KktParams K{};
-  K.meta = s->buf.d_meta; // the caller-facing records, also on a folded solver (d_meta2 / d_prob2 stay inside the library)
-  K.prob = s->buf.d_prob;
-  K.sol = s->buf.d_sol;
-  K.theta = theta_dev;
-  K.stage = s->buf.d_kkt_stage;
-  K.err = s->buf.d_kkt_err;
-  K.prob_stride = s->prob_doubles;
-  K.sol_stride = s->sol_doubles;
-  K.G0_off = s->G0_off;
-  K.g0_off = s->g0_off;
-  K.horizon = s->horizon;
-  K.nc0 = s->nc0;
-  K.nth0 = s->nth0;
-  K.qr_packed = s->qr_packed ? 1 : 0;
-  K.mueq = mueq;
-  return K;
-}
-
-// the two result buffers, on the first call after the layout was built (both or neither), and the kernel's LDS
-int kkt_buffers(gar_hip_solver *s) {
-  if (s->buf.d_kkt_stage)
-    return GAR_HIP_OK;
-  if ((int64_t)s->batch * (s->horizon + 1) > INT32_MAX) // one workgroup per (problem, stage), all of them in grid.x
-    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_kkt_error: batch x (horizon + 1) above 2^31 - 1 workgroups");
-  int lds = 0; // (the knot is tiled, the stage's vectors are not: they bound the dimensions, below)
-  for (const gar_stage_meta &m : s->meta)
-    lds = std::max(lds, gar::kkt_lds_doubles(m.nx, m.nu, m.nc, m.nx2, m.nth, s->nc0));
-  const size_t bytes = (size_t)lds * sizeof(double);
-  if (bytes > kCuLdsBytes)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_kkt_error: the stage vectors need " + std::to_string(bytes) +
-                                             " B of LDS (> 160 KiB per CU)");
-  HIP_TRY(max_lds(gar::gar_kkt_stage_residuals, (size_t)lds));
-  DevBuf<double> st, er;
-  HIP_TRY(st.zalloc((size_t)s->batch * (size_t)(s->horizon + 1) * 4));
-  HIP_TRY(er.zalloc((size_t)s->batch * 3));
-  s->buf.d_kkt_stage = std::move(st);
-  s->buf.d_kkt_err = std::move(er);
-  s->buf.kkt_lds_bytes = bytes;
-  return GAR_HIP_OK;
-}
-
-// the kernel pair: a workgroup per (problem, stage), then the fold of the stage norms, a wave per problem
-int launch_kkt_pair(gar_hip_solver *s, const gar::KktParams &K) {
-  hipLaunchKernelGGL(gar::gar_kkt_stage_residuals, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)),
-                     dim3(GAR_KKT_THREADS), s->buf.kkt_lds_bytes, s->stream, K);
-  hipLaunchKernelGGL(gar::gar_kkt_reduce, dim3((unsigned)s->batch), dim3(64), 0, s->stream, K);
-  HIP_TRY(hipGetLastError());
-  return GAR_HIP_OK;
-}
-
-int launch_kkt(gar_hip_solver *s, double mueq, const double *theta_dev) {
-  RoctxRange range_("gar::lqrComputeKktError");
-  if (int rc = kkt_buffers(s))
-    return rc;
-  if (int rc = commit(s)) // knots the host staged since the last sweep
-    return rc;
-  return launch_kkt_pair(s, make_kkt_params(s, mueq, theta_dev));
-}
-
-// ---- the re-solve for new affine terms (gar_affine.hpp): scatter, prepare, the vector sweep, the initial stage -----------
-// doubles of one problem's affine vector and the offsets of its stages (q_t | r_t | f_t ... g0), the CALLER's dimensions;
-// a terminal knot given with nx2 = 0 has no f
-int64_t affine_offsets(const gar_hip_solver *s, std::vector<long long> *off) {
-  const int N = s->horizon;
-  long long p = 0;
-  if (off)
-    off->assign((size_t)N + 2, 0);
-  for (int t = 0; t <= N; ++t) {
-    const int32_t *d = &s->user_dims5[5 * (size_t)t];
-    if (off)
-      (*off)[(size_t)t] = p;
-    p += d[0] + d[1] + ((s->term_grown && t == N) ? 0 : d[3]);
-  }
-  if (off)
-    (*off)[(size_t)N + 1] = p;
-  return p + s->user_nc0;
-}
-
-// who is served: serial in time, one device, nc = nth = 0 on every knot, the stand-alone initial stage of one wave
-int affine_check(const gar_hip_solver *s, const char *who) {
-  if (!s)
-    return fail(GAR_HIP_ERR_ARG, "null solver");
-  const std::string w(who);
-  if (s->multi)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, w + ": a multi-device solver is not served (the records live on several devices)");
-  if (s->dense)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, w + ": the stage-dense solver is not served");
-  if (s->num_legs != 1 || s->world != 1)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, w + ": leg mode is not served (num_legs = 1 only)");
-  if (s->fold)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, w + ": a folded solver (constrained knots) is not served");
-  for (int t = 0; t <= s->horizon; ++t) {
-    const int32_t *d = &s->dims5[5 * (size_t)t];
-    if (d[2] != 0 || d[4] != 0)
-      return fail(GAR_HIP_ERR_UNSUPPORTED, w + ": knot " + std::to_string(t) + " is constrained or parameterised (nc = nth = 0 only)");
-  }
-  if (s->n0 > 128)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, w + ": nx + nc0 above 128 (the stand-alone initial stage of one wave)");
-  return GAR_HIP_OK;
-}
-
-gar::AffineParams make_affine_params(gar_hip_solver *s) {
-  gar::AffineParams A{};
-  A.meta = s->buf.d_meta;
-  A.prob = s->buf.d_prob;
-  A.fac = s->buf.d_fac;
-  A.W = s->buf.d_aff_W;
-  A.status = status_words(s);
-  A.ok = s->buf.d_aff_ok;
-  A.src_off = s->buf.d_aff_off;
-  A.prob_stride = s->prob_doubles;
-  A.fac_stride = s->fac_doubles;
-  A.src_stride = affine_offsets(s, nullptr);
-  A.g0_off = s->g0_off;
-  A.horizon = s->horizon;
-  A.w_rec = s->buf.aff_w_rec;
-  A.unx = s->padded ? s->unx : 0;
-  A.unu = s->padded ? s->unu : 0;
-  A.unc0 = s->user_nc0;
-  A.qr_packed = s->qr_packed ? 1 : 0;
-  A.vxx_packed = s->vxx_packed ? 1 : 0;
-  A.fb_t2 = s->fb_t2 ? 1 : 0;
-  A.nx_max = s->buf.aff_nx_max;
-  return A;
-}
-
-// the side buffers, on the first call after the layout was built (all or none), and the two kernels' LDS
-int affine_buffers(gar_hip_solver *s) {
-  if (s->buf.d_aff_off)
-    return GAR_HIP_OK;
-  if ((int64_t)s->batch * (s->horizon + 1) > INT32_MAX)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_backward_affine: batch x (horizon + 1) above 2^31 - 1 workgroups");
-  int nu_max = 0, nx_max = 0, lds = 0, plds = 0;
-  for (const gar_stage_meta &m : s->meta) {
-    nu_max = std::max(nu_max, (int)m.nu);
-    nx_max = std::max(nx_max, std::max((int)m.nx, (int)m.nx2));
-  }
-  for (const gar_stage_meta &m : s->meta) {
-    lds = std::max(lds, gar::affine_sweep_lds_doubles(nx_max, m.nx, m.nu, m.nx2, s->fb_t2, s->vxx_packed));
-    plds = std::max(plds, gar::affine_prepare_lds_doubles(m.nu, m.nx2, s->vxx_packed));
-  }
-  if ((size_t)std::max(lds, plds) * sizeof(double) > kCuLdsBytes)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_backward_affine: a stage's blocks need " +
-                                             std::to_string((size_t)std::max(lds, plds) * sizeof(double)) + " B of LDS (> 160 KiB per CU)");
-  HIP_TRY(max_lds(gar::gar_backward_affine, (size_t)lds));
-  HIP_TRY(max_lds(gar::gar_affine_prepare, (size_t)plds));
-  std::vector<long long> off;
-  affine_offsets(s, &off);
-  const int w_rec = std::max(2, (nu_max * nu_max + 1) & ~1);
-  DevBuf<double> W;
-  DevBuf<int> ok;
-  DevBuf<long long> doff;
-  HIP_TRY(W.zalloc((size_t)s->batch * (size_t)(s->horizon + 1) * (size_t)w_rec));
-  HIP_TRY(ok.zalloc((size_t)s->batch));
-  HIP_TRY(doff.alloc(off.size()));
-  HIP_TRY(hipMemcpy(doff, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice));
-  s->buf.d_aff_W = std::move(W);
-  s->buf.d_aff_ok = std::move(ok);
-  s->buf.d_aff_off = std::move(doff);
-  s->buf.aff_w_rec = w_rec;
-  s->buf.aff_nx_max = nx_max;
-  s->buf.aff_lds_bytes = (size_t)lds * sizeof(double);
-  s->buf.aff_prep_lds_bytes = (size_t)plds * sizeof(double);
-  s->cur.W_allocated();
-  return GAR_HIP_OK;
-}
-
-// nb affine vectors at the DEVICE address src into the knots of problems b0 ..: staged host blocks go out first, so
-// that no later flush writes older q, r, f over these
-int launch_affine_scatter(gar_hip_solver *s, int b0, int nb, const double *src_dev) {
-  if (nb == 0)
-    return GAR_HIP_OK;
-  if (int rc = commit(s))
-    return rc;
-  gar::AffineParams A = make_affine_params(s);
-  A.src = src_dev;
-  A.b0 = b0;
-  hipLaunchKernelGGL(gar::gar_affine_scatter, dim3((unsigned)nb * (unsigned)(s->horizon + 1)), dim3(64), 0, s->stream, A);
-  HIP_TRY(hipGetLastError());
-  return GAR_HIP_OK;
-}
-
-// W = Rhat^-1 of every stage, formed once per factorisation: by the first re-solve or refinement step that needs it
-int ensure_W(gar_hip_solver *s, const gar::AffineParams &A) {
-  if (s->cur.W_valid)
-    return GAR_HIP_OK;
-  hipLaunchKernelGGL(gar::gar_affine_prepare, dim3((unsigned)s->batch * (unsigned)(s->horizon + 1)), dim3(64),
-                     s->buf.aff_prep_lds_bytes, s->stream, A);
-  HIP_TRY(hipGetLastError());
-  s->cur.W_formed();
-  return GAR_HIP_OK;
-}
-
-int launch_backward_affine(gar_hip_solver *s) {
-  RoctxRange range_("gar::backward_affine");
-  s->cur.solution_superseded(); // (the roll-out in HBM stays a solution gar_hip_refine may start from)
-  if (int rc = settle_gains_readback(s, kBehindStream))
-    return rc;
-  if (int rc = commit(s)) // (a g0 staged through gar_hip_set_init)
-    return rc;
-  const gar::AffineParams A = make_affine_params(s);
-  if (int rc = ensure_W(s, A))
-    return rc;
-  hipLaunchKernelGGL(gar::gar_backward_affine, dim3((unsigned)s->batch), dim3(64), s->buf.aff_lds_bytes, s->stream, A);
-  // the initial stage: the stand-alone kernel backward_serial launches for the families that do not fuse it, on the
-  // problems the sweep took (kkt0 is factorised again: its matrix is not kept)
-  gar::GenericParams I = make_params(s, s->cur.mueq);
-  I.only = s->buf.d_aff_ok;
-  hipLaunchKernelGGL(gar::gar_initial_wave, dim3((unsigned)s->batch), dim3(64),
-                     (size_t)gar::gar_initial_wave_lds_doubles(s->n0, s->nth0) * sizeof(double), s->stream, I);
-  HIP_TRY(hipGetLastError());
-  return GAR_HIP_OK;
-}
-
-// ---- one refinement step from the stored factorisation (gar_refine.hpp): residual vectors, sweep, initial stage, roll-out --
-// the side buffers, on the first call after the layout was built (all or none), and the three kernels' LDS
-int refine_buffers(gar_hip_solver *s) {
-  if (s->buf.d_ref_gate)
-    return GAR_HIP_OK;
-  const int nx_max = s->buf.aff_nx_max; // (affine_buffers ran)
-  int rhs_rec = 2, out_rec = 2, lds = 0, rlds = 0;
-  for (const gar_stage_meta &m : s->meta) {
-    rhs_rec = std::max(rhs_rec, gar::refine_rhs_f(m.nx, m.nu) + ((m.nx2 + 1) & ~1));
-    out_rec = std::max(out_rec, gar::refine_out_vx(m.nu, m.nx2) + ((m.nx + 1) & ~1));
-    lds = std::max(lds, gar::affine_sweep_lds_doubles(nx_max, m.nx, m.nu, m.nx2, s->fb_t2, s->vxx_packed) + 4);
-    rlds = std::max(rlds, gar::refine_rollout_lds_doubles(nx_max, m.nx, m.nu, m.nx2, s->fb_t2, s->vxx_packed));
-  }
-  const int ilds = gar::gar_initial_wave_lds_doubles(s->n0, s->nth0);
-  if ((size_t)std::max(lds, std::max(rlds, ilds)) * sizeof(double) > kCuLdsBytes)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_refine: a stage's blocks need " +
-                                             std::to_string((size_t)std::max(lds, std::max(rlds, ilds)) * sizeof(double)) +
-                                             " B of LDS (> 160 KiB per CU)");
-  HIP_TRY(max_lds(gar::gar_refine_sweep, (size_t)lds));
-  HIP_TRY(max_lds(gar::gar_refine_rollout, (size_t)rlds));
-  HIP_TRY(max_lds(gar::gar_refine_initial, (size_t)ilds));
-  const int N = s->horizon, init_rec = std::max(2, (s->n0 + 1) & ~1);
-  const long long rhs_stride = (long long)(N + 1) * rhs_rec + ((s->nc0 + 1) & ~1) + 2;
-  const long long out_stride = (long long)(N + 1) * out_rec + 2; // (+ 2: the last stage names a record behind its own)
-  DevBuf<double> rhs, out, init;
-  DevBuf<int> gate;
-  HIP_TRY(rhs.zalloc((size_t)s->batch * (size_t)rhs_stride));
-  HIP_TRY(out.zalloc((size_t)s->batch * (size_t)out_stride));
-  HIP_TRY(init.zalloc((size_t)s->batch * (size_t)init_rec));
-  HIP_TRY(gate.zalloc((size_t)s->batch));
-  s->buf.d_ref_rhs = std::move(rhs);
-  s->buf.d_ref_out = std::move(out);
-  s->buf.d_ref_init = std::move(init);
-  s->buf.d_ref_gate = std::move(gate);
-  s->buf.ref_rhs_rec = rhs_rec, s->buf.ref_out_rec = out_rec, s->buf.ref_init_rec = init_rec;
-  s->buf.ref_rhs_stride = rhs_stride, s->buf.ref_out_stride = out_stride;
-  s->buf.ref_sweep_lds_bytes = (size_t)lds * sizeof(double);
-  s->buf.ref_roll_lds_bytes = (size_t)rlds * sizeof(double);
-  s->buf.ref_init_lds_bytes = (size_t)ilds * sizeof(double);
-  return GAR_HIP_OK;
-}
-
-// the KKT buffers of the solution in HBM (what gar_hip_kkt_error_async writes, at the mueq of the backward being reused),
-// the residual vectors into the right-hand side and the gate words of the next step
-int launch_refine_residual(gar_hip_solver *s, double threshold) {
-  gar::KktParams K = make_kkt_params(s, s->cur.mueq, nullptr);
-  K.rhs = s->buf.d_ref_rhs;
-  K.gate = s->buf.d_ref_gate;
-  K.status = status_words(s);
-  K.rhs_stride = s->buf.ref_rhs_stride;
-  K.rhs_rec = s->buf.ref_rhs_rec;
-  K.threshold = threshold;
-  return launch_kkt_pair(s, K);
-}
-
-// the parameter blocks of the redirected sweep, its initial stage and its roll-out: the refinement's side buffers, the
-// gate words of the caller (the refinement's, or the adjoint's "status word zero")
-void make_refine_params(gar_hip_solver *s, const int *gate, gar::AffineParams &A, gar::RefineParams &R) {
-  A = make_affine_params(s);
-  A.rhs = s->buf.d_ref_rhs;
-  A.out = s->buf.d_ref_out;
-  A.gate = gate;
-  A.rhs_stride = s->buf.ref_rhs_stride, A.out_stride = s->buf.ref_out_stride;
-  A.rhs_rec = s->buf.ref_rhs_rec, A.out_rec = s->buf.ref_out_rec;
-  R = gar::RefineParams{};
-  R.G = make_params(s, s->cur.mueq);
-  R.rhs = A.rhs, R.out = A.out, R.init = s->buf.d_ref_init, R.gate = A.gate;
-  R.rhs_stride = A.rhs_stride, R.out_stride = A.out_stride, R.init_rec = s->buf.ref_init_rec;
-  R.rhs_rec = A.rhs_rec, R.out_rec = A.out_rec;
-  R.fb_t2 = A.fb_t2, R.nx_max = A.nx_max;
-}
-
-// the correction of the gated problems, added to the solution records
-int launch_refine_correction(gar_hip_solver *s) {
-  gar::AffineParams A;
-  gar::RefineParams R;
-  make_refine_params(s, s->buf.d_ref_gate, A, R);
-  if (int rc = ensure_W(s, A))
-    return rc;
-  const dim3 grid((unsigned)s->batch), wave(64);
-  hipLaunchKernelGGL(gar::gar_refine_sweep, grid, wave, s->buf.ref_sweep_lds_bytes, s->stream, A);
-  hipLaunchKernelGGL(gar::gar_refine_initial, grid, wave, s->buf.ref_init_lds_bytes, s->stream, R);
-  hipLaunchKernelGGL(gar::gar_refine_rollout, grid, wave, s->buf.ref_roll_lds_bytes, s->stream, R);
-  HIP_TRY(hipGetLastError());
-  return GAR_HIP_OK;
-}
-
-// ---- gradients of a resident batch (gar_adjoint.hpp): the caller's packed layout on the device, the adjoint solve -------
-// a padded solver's caller-side knot offsets on the device (the caller's layout does not turn with the ring); an unpadded
-// solver's are the device's own stage descriptors
-int user_layout_buffers(gar_hip_solver *s) {
-  if (!s->padded || s->buf.d_adj_uoff)
-    return GAR_HIP_OK;
-  std::vector<long long> off;
-  for (const gar_stage_meta &m : s->ulay->meta)
-    off.push_back(m.in_off);
-  DevBuf<long long> d;
-  HIP_TRY(d.alloc(off.size()));
-  HIP_TRY(hipMemcpy(d, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice));
-  s->buf.d_adj_uoff = std::move(d);
-  return GAR_HIP_OK;
-}
-
-// (affine_buffers ran: the offsets of the affine layout are on the device)
-gar::AdjointParams make_adjoint_params(gar_hip_solver *s) {
-  const gar::HostLayout &u = caller_layout(s);
-  gar::AdjointParams P{};
-  P.meta = s->buf.d_meta;
-  P.U.in_off = s->padded ? s->buf.d_adj_uoff.get() : nullptr;
-  P.U.stride = u.prob_doubles, P.U.G0_off = u.G0_off, P.U.g0_off = u.g0_off;
-  P.U.unx = s->padded ? s->unx : 0, P.U.unu = s->padded ? s->unu : 0;
-  P.U.nc0 = s->user_nc0;
-  P.vec_off = s->buf.d_aff_off;
-  P.vec_stride = affine_offsets(s, nullptr);
-  P.status = status_words(s);
-  P.rhs = s->buf.d_ref_rhs;
-  P.gate = s->buf.d_adj_gate;
-  P.rhs_stride = s->buf.ref_rhs_stride;
-  P.rhs_rec = s->buf.ref_rhs_rec;
-  P.sol = s->buf.d_sol;
-  P.adj = s->buf.d_adj_rec;
-  P.sol_stride = s->sol_doubles;
-  P.prob = s->buf.d_prob;
-  P.prob_stride = s->prob_doubles, P.G0_off = s->G0_off, P.g0_off = s->g0_off;
-  P.horizon = s->horizon, P.nc0 = s->nc0, P.nx0 = s->nx0;
-  P.qr_packed = s->qr_packed ? 1 : 0;
-  return P;
-}
-
-// the adjoint records, the gate words and the LDS of the two kernels with dynamic LDS, on the first call after the layout
-// was built (affine_buffers and refine_buffers ran)
-int adjoint_buffers(gar_hip_solver *s) {
-  if (s->buf.d_adj_gate)
-    return GAR_HIP_OK;
-  if (int rc = user_layout_buffers(s))
-    return rc;
-  int glds = 0;
-  for (const gar_stage_meta &m : s->meta) // (the device's dimensions bound the caller's)
-    glds = std::max(glds, gar::adjoint_grad_lds_doubles(m.nx, m.nu, m.nx2, s->nc0, s->nx0));
-  if ((size_t)glds * sizeof(double) > kCuLdsBytes)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_adjoint: a knot of the gradient record needs " +
-                                             std::to_string((size_t)glds * sizeof(double)) + " B of LDS (> 160 KiB per CU)");
-  HIP_TRY(max_lds(gar::gar_adjoint_gradients, (size_t)glds));
-  HIP_TRY(max_lds(gar::gar_adjoint_rollout, s->buf.ref_roll_lds_bytes / sizeof(double)));
-  DevBuf<double> rec;
-  DevBuf<int> gate;
-  HIP_TRY(rec.zalloc((size_t)s->batch * (size_t)s->sol_doubles));
-  HIP_TRY(gate.zalloc((size_t)s->batch));
-  s->buf.d_adj_rec = std::move(rec);
-  s->buf.d_adj_gate = std::move(gate);
-  s->buf.adj_grad_lds_bytes = (size_t)glds * sizeof(double);
-  return GAR_HIP_OK;
-}
-
-// nb packed problems in the caller's layout at the DEVICE address src into the knots of problems b0 ...
-int launch_user_upload(gar_hip_solver *s, int b0, int nb, const double *src_dev) {
-  if (nb == 0)
-    return GAR_HIP_OK;
-  gar::AdjointParams P = make_adjoint_params(s);
-  P.user = src_dev;
-  P.b0 = b0;
-  hipLaunchKernelGGL(gar::gar_user_upload_scatter, dim3((unsigned)nb * (unsigned)(s->horizon + 1)), dim3(GAR_ADJ_THREADS), 0,
-                     s->stream, P);
-  HIP_TRY(hipGetLastError());
-  return GAR_HIP_OK;
-}
-
-// records (the solution's or the adjoint's) of problems b0 ... as nb vectors of the affine layout at the DEVICE address out
-int launch_solution_gather(gar_hip_solver *s, int b0, int nb, const double *rec_dev, double *out_dev) {
-  if (nb == 0)
-    return GAR_HIP_OK;
-  gar::AdjointParams P = make_adjoint_params(s);
-  P.rec = rec_dev;
-  P.vec = out_dev;
-  P.b0 = b0;
-  hipLaunchKernelGGL(gar::gar_solution_gather, dim3((unsigned)nb * (unsigned)(s->horizon + 1)), dim3(64), 0, s->stream, P);
-  HIP_TRY(hipGetLastError());
-  return GAR_HIP_OK;
-}
-
-// the cotangents at cot_dev -> the adjoint records; their affine-layout vectors to adj_dev and the gradient records to
-// grad_dev where asked for.  Nothing of the primal is written.
-int launch_adjoint(gar_hip_solver *s, const double *cot_dev, double *adj_dev, double *grad_dev) {
-  RoctxRange range_("gar::adjoint");
-  gar::AffineParams A;
-  gar::RefineParams R;
-  make_refine_params(s, s->buf.d_adj_gate, A, R);
-  gar::RefineParams Radj = R; // the roll-out's "solution" is the adjoint record
-  Radj.G.sol = s->buf.d_adj_rec;
-  if (int rc = ensure_W(s, A))
-    return rc;
-  gar::AdjointParams P = make_adjoint_params(s);
-  P.cot = cot_dev;
-  P.grad = grad_dev;
-  const dim3 grid((unsigned)s->batch), stages((unsigned)s->batch * (unsigned)(s->horizon + 1)), wave(64);
-  hipLaunchKernelGGL(gar::gar_adjoint_scatter, stages, wave, 0, s->stream, P);
-  hipLaunchKernelGGL(gar::gar_refine_sweep, grid, wave, s->buf.ref_sweep_lds_bytes, s->stream, A);
-  hipLaunchKernelGGL(gar::gar_refine_initial, grid, wave, s->buf.ref_init_lds_bytes, s->stream, R);
-  hipLaunchKernelGGL(gar::gar_adjoint_rollout, grid, wave, s->buf.ref_roll_lds_bytes, s->stream, Radj);
-  HIP_TRY(hipGetLastError());
-  if (adj_dev)
-    if (int rc = launch_solution_gather(s, 0, s->batch, s->buf.d_adj_rec, adj_dev))
-      return rc;
-  if (grad_dev) {
-    hipLaunchKernelGGL(gar::gar_adjoint_gradients, stages, dim3(GAR_ADJ_THREADS), s->buf.adj_grad_lds_bytes, s->stream, P);
-    HIP_TRY(hipGetLastError());
-  }
-  return GAR_HIP_OK;
-}
-
-// ---- many affine terms at once (gar_affine_multi.hpp): panel scatter, the MFMA sweep, the initial stage, the MFMA roll-out ----
-// bytes of the work buffers of one panel of one problem (the header's formula): the two panel records of every stage and
-// the initial stage's three vectors of 16 columns
-size_t affine_multi_panel_bytes(const gar_hip_solver *s, int prhs_rec, int pout_rec, int ivx_rec, int ig0_rec, int init_rec) {
-  return sizeof(double) * ((size_t)(s->horizon + 1) * (size_t)(prhs_rec + pout_rec) +
-                           (size_t)GAR_AM_COLS * (size_t)(ivx_rec + ig0_rec + init_rec));
-}
-// the work buffers of one chunk and the gate words, on the first call after the layout was built (all or none; a failed
-// allocation leaves the solver as it was), and the three kernels' LDS (affine_buffers ran)
-int affine_multi_buffers(gar_hip_solver *s) {
-  if (s->buf.d_am_gate)
-    return GAR_HIP_OK;
-  const int nx_max = s->buf.aff_nx_max, N = s->horizon, C = GAR_AM_COLS;
-  int nu_max = 0, rows = 1, lds = 0, rlds = 0;
-  for (const gar_stage_meta &m : s->meta)
-    nu_max = std::max(nu_max, (int)m.nu);
-  for (const gar_stage_meta &m : s->meta) {
-    rows = std::max(rows, (int)(m.nx + m.nu + m.nx2));
-    lds = std::max(lds, gar::affine_multi_sweep_lds_doubles(nx_max, nu_max, m.nx, m.nu, m.nx2, s->fb_t2, s->vxx_packed));
-    rlds = std::max(rlds, gar::affine_multi_rollout_lds_doubles(nx_max, nu_max, m.nx, m.nu, m.nx2, s->fb_t2, s->vxx_packed));
-  }
-  const int ilds = gar::gar_initial_wave_lds_doubles(s->n0, s->nth0);
-  if ((size_t)std::max(lds, std::max(rlds, ilds)) * sizeof(double) > kCuLdsBytes)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_affine_solve_multi: a stage's blocks and panels need " +
-                                             std::to_string((size_t)std::max(lds, std::max(rlds, ilds)) * sizeof(double)) +
-                                             " B of LDS (> 160 KiB per CU)");
-  const int rec = C * rows, ivx_rec = std::max(2, (s->nx0 + 1) & ~1), ig0_rec = std::max(2, (s->nc0 + 1) & ~1);
-  const int init_rec = std::max(2, (s->n0 + 1) & ~1);
-  // panels per problem in a chunk: enough workgroups for the device at a small batch, at most 1 GiB of work buffers
-  const size_t per_panel = affine_multi_panel_bytes(s, rec, rec, ivx_rec, ig0_rec, init_rec);
-  int panels = std::min(8, std::max(1, (1024 + s->batch - 1) / s->batch));
-  while (panels > 1 && per_panel * (size_t)s->batch * (size_t)panels > ((size_t)1 << 30))
-    --panels;
-  if ((int64_t)s->batch * panels * std::max(N + 1, C) > INT32_MAX)
-    return fail(GAR_HIP_ERR_UNSUPPORTED, "gar_hip_affine_solve_multi: batch x (horizon + 1) above 2^31 - 1 workgroups");
-  const size_t bp = (size_t)s->batch * (size_t)panels;
-  const long long stride = (long long)(N + 1) * rec;
-  DevBuf<double> rhs, out, ivx, ig0, ires;
-  DevBuf<int> gate;
-  hipError_t e = rhs.zalloc(bp * (size_t)stride);
-  e = e != hipSuccess ? e : out.zalloc(bp * (size_t)stride);
-  e = e != hipSuccess ? e : ivx.zalloc(bp * C * (size_t)ivx_rec);
-  e = e != hipSuccess ? e : ig0.zalloc(bp * C * (size_t)ig0_rec);
-  e = e != hipSuccess ? e : ires.zalloc(bp * C * (size_t)init_rec);
-  e = e != hipSuccess ? e : gate.zalloc((size_t)s->batch);
-  if (e != hipSuccess) {
-    (void)hipGetLastError(); // (the error is reported here; the next launch check of this solver starts clean)
-    return fail(GAR_HIP_ERR_DEVICE, "gar_hip_affine_solve_multi: " + std::to_string(per_panel * bp + sizeof(int) * (size_t)s->batch) +
-                                        " B of work buffers: " + hipGetErrorString(e));
-  }
-  HIP_TRY(max_lds(gar::gar_affine_sweep_multi, (size_t)lds));
-  HIP_TRY(max_lds(gar::gar_rollout_multi, (size_t)rlds));
-  HIP_TRY(max_lds(gar::gar_affine_multi_initial, (size_t)ilds));
-  s->buf.d_am_rhs = std::move(rhs), s->buf.d_am_out = std::move(out);
-  s->buf.d_am_ivx = std::move(ivx), s->buf.d_am_ig0 = std::move(ig0), s->buf.d_am_ires = std::move(ires);
-  s->buf.d_am_gate = std::move(gate);
-  s->buf.am_panels = panels, s->buf.am_nu_max = nu_max;
-  s->buf.am_prhs_rec = s->buf.am_pout_rec = rec;
-  s->buf.am_ivx_rec = ivx_rec, s->buf.am_ig0_rec = ig0_rec, s->buf.am_init_rec = init_rec;
-  s->buf.am_prhs_stride = s->buf.am_pout_stride = stride;
-  s->buf.am_sweep_lds_bytes = (size_t)lds * sizeof(double);
-  s->buf.am_roll_lds_bytes = (size_t)rlds * sizeof(double);
-  s->buf.am_init_lds_bytes = (size_t)ilds * sizeof(double);
-  return GAR_HIP_OK;
-}
-
-// columns [0, nrhs) of every problem: rhs_dev and out_dev are [batch][nrhs][affine doubles] at DEVICE addresses.  The host
-// loops over chunks of am_panels panels; every kernel of a chunk is ordered behind the previous chunk's on the stream.
-int launch_affine_multi(gar_hip_solver *s, int nrhs, const double *rhs_dev, double *out_dev) {
-  RoctxRange range_("gar::affine_solve_multi");
-  const gar::AffineParams A = make_affine_params(s);
-  if (int rc = ensure_W(s, A))
-    return rc;
-  gar::AffineMultiParams P{};
-  P.meta = s->buf.d_meta;
-  P.U.unx = s->padded ? s->unx : 0, P.U.unu = s->padded ? s->unu : 0;
-  P.U.nc0 = s->user_nc0;
-  P.vec_off = s->buf.d_aff_off;
-  P.vec_stride = affine_offsets(s, nullptr);
-  P.status = status_words(s);
-  P.prob = s->buf.d_prob, P.fac = s->buf.d_fac, P.W = s->buf.d_aff_W;
-  P.prob_stride = s->prob_doubles, P.fac_stride = s->fac_doubles;
-  P.w_rec = s->buf.aff_w_rec, P.horizon = s->horizon, P.nc0 = s->nc0;
-  P.vxx_packed = A.vxx_packed, P.fb_t2 = A.fb_t2;
-  P.nrhs = nrhs;
-  P.rhs = rhs_dev, P.out = out_dev;
-  P.prhs = s->buf.d_am_rhs, P.pout = s->buf.d_am_out;
-  P.ivx = s->buf.d_am_ivx, P.ig0 = s->buf.d_am_ig0, P.ires = s->buf.d_am_ires;
-  P.gate = s->buf.d_am_gate;
-  P.prhs_stride = s->buf.am_prhs_stride, P.pout_stride = s->buf.am_pout_stride;
-  P.prhs_rec = s->buf.am_prhs_rec, P.pout_rec = s->buf.am_pout_rec;
-  P.ivx_rec = s->buf.am_ivx_rec, P.ig0_rec = s->buf.am_ig0_rec, P.init_rec = s->buf.am_init_rec;
-  P.nx_max = s->buf.aff_nx_max, P.nu_max = s->buf.am_nu_max;
-  gar::AffineMultiInit I{};
-  I.G = make_params(s, s->cur.mueq);
-  I.ivx = P.ivx, I.ig0 = P.ig0, I.ires = P.ires, I.gate = P.gate;
-  I.ivx_rec = P.ivx_rec, I.ig0_rec = P.ig0_rec, I.init_rec = P.init_rec;
-  const int C = GAR_AM_COLS, total = (nrhs + C - 1) / C;
-  for (int p0 = 0; p0 < total; p0 += s->buf.am_panels) {
-    P.c0 = p0 * C;
-    P.panels = I.panels = std::min(s->buf.am_panels, total - p0);
-    const unsigned groups = (unsigned)s->batch * (unsigned)P.panels;
-    hipLaunchKernelGGL(gar::gar_affine_multi_scatter, dim3(groups * (unsigned)(s->horizon + 1)), dim3(GAR_AM_THREADS), 0,
-                       s->stream, P);
-    hipLaunchKernelGGL(gar::gar_affine_sweep_multi, dim3(groups), dim3(GAR_AM_THREADS), s->buf.am_sweep_lds_bytes, s->stream, P);
-    hipLaunchKernelGGL(gar::gar_affine_multi_initial, dim3(groups * (unsigned)C), dim3(64), s->buf.am_init_lds_bytes, s->stream, I);
-    hipLaunchKernelGGL(gar::gar_rollout_multi, dim3(groups), dim3(GAR_AM_THREADS), s->buf.am_roll_lds_bytes, s->stream, P);
-    HIP_TRY(hipGetLastError());
-  }
   return GAR_HIP_OK;
 }

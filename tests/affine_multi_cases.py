@@ -379,6 +379,58 @@ def check_allocation(lib_path, rounds=20, mueq=1e-10):
     assert_columns(results[40].reshape(sets[40].shape), yardsticks(s, probs, sets[40], mueq, only=(1,)), label="allocation nrhs=40")
 
 
+def same_solutions(s, other, label):
+    for b in range(s.batch):
+        for part, want in zip(s.solution(b), other.solution(b)):
+            assert len(part) == len(want) and all(np.array_equal(bits(x), bits(y)) for x, y in zip(part, want)), (label, b)
+
+
+def check_rebuild_with_services_live(lib_path, mueq=1e-10):
+    """case 15: two cycleAppends that change the dimensions while the work areas of every resident-batch service are live:
+    they go with the layout, and what the next calls build serves the new dimensions -- the bits of a fresh solver"""
+    nx, nu, N = 8, 4, 3
+    probs = rc.singular_problems(nx, nu, N, 2)
+    rng = np.random.default_rng(115)
+    s = rc.solved(probs, lib_path, mueq, BACKWARD="wave")
+    s.kkt_error(mueq)
+    assert s.refine(1) == (1, 2)
+    s.adjoint(adc.cotangents(s, rng))
+    s.affine_solve_multi(right_hand_sides(s, 17, rng))
+    ac.resolve(s, [ac.substituted(p, rng) for p in probs])
+    assert s.affine_doubles == (N + 1) * 2 * nx + N * nu + nx == 84
+    assert all(s.device_kkt_errors()) and s.device_adjoints()
+    for nu_new, doubles in ((5, 85), (3, 84)):
+        s.cycle_append((nx, nu_new, 0, nx, 0))
+        assert s.device_kkt_errors() == (None, None) and not s.device_adjoints()
+        new = []
+        for p in probs:
+            q = p.copy()
+            q.stages[:N] = q.stages[1:N] + [synth.generate_knot(rng, nx, nu_new, 0, mode="W")]
+            new.append(q)
+        probs = new
+        s.upload(probs)
+        fresh = kc.solver_for(probs, lib_path)
+        assert s.kernel_name == fresh.kernel_name == "generic", (s.kernel_name, fresh.kernel_name)
+        assert s.affine_doubles == fresh.affine_doubles == doubles
+        for q in (s, fresh):
+            assert q.backward(mueq) and q.forward()
+        label = f"rebuilt, appended nu={nu_new}"
+        rhs = right_hand_sides(s, 17, rng)
+        out = s.affine_solve_multi(rhs)
+        assert np.array_equal(bits(out), bits(fresh.affine_solve_multi(rhs))), label
+        assert_columns(out, yardsticks(s, probs, rhs, mueq), label=label)
+        cot = adc.cotangents(s, rng)
+        for a, b in zip(s.adjoint(cot), fresh.adjoint(cot)):
+            assert np.array_equal(bits(a), bits(b)), label
+        assert s.refine(1) == fresh.refine(1), label
+        same_solutions(s, fresh, label)
+        others = [ac.substituted(p, rng) for p in probs]
+        for q in (s, fresh):
+            ac.resolve(q, others)
+        same_solutions(s, fresh, label)
+        assert np.array_equal(s.kkt_error(mueq), fresh.kkt_error(mueq)), label
+
+
 def check_no_host_sync(lib_path, mueq=1e-10, pipeline=False, nrhs=19):
     """case 13: upload_packed_user_device -> backward_async -> affine_solve_multi_async -> sync with no host wait in
     between: bitwise what the synchronous calls give (adjoint_cases.check_no_host_sync's check)"""

@@ -311,6 +311,54 @@ void refusals() {
   }
 }
 
+// 9: every service on a resident batch (KKT residuals, re-solve, refinement, adjoint with gradients, many affine terms, the
+// device-resident caller's two calls) with its work area live at a ring cycle_append, at a rebuilding one and at destroy.
+// (Unconstrained: scenario 1's terminal constraints make these services refuse.)
+void resident_calls(gar_hip_solver *s, int batch) {
+  const size_t n = (size_t)gar_hip_affine_doubles(s) * (size_t)batch, np = (size_t)gar_hip_problem_doubles(s) * (size_t)batch;
+  std::vector<double> vec(n), adj(n), grad(np), rhs(17 * n), out(17 * n), packed(np);
+  for (std::vector<double> *v : {&vec, &rhs})
+    for (double &x : *v)
+      x = rnd();
+  double kkt[6];
+  CHECK(gar_hip_kkt_error(s, kMu, nullptr, kkt, nullptr) == GAR_HIP_OK);
+  CHECK(gar_hip_upload_affine(s, 0, batch, vec.data()) == GAR_HIP_OK);
+  CHECK(gar_hip_backward_affine(s) == GAR_HIP_OK);
+  CHECK(gar_hip_forward(s, nullptr) == GAR_HIP_OK);
+  int32_t steps[2];
+  CHECK(gar_hip_refine(s, 1, -1.0, steps) == GAR_HIP_OK);
+  CHECK(gar_hip_adjoint(s, vec.data(), adj.data(), grad.data()) == GAR_HIP_OK);
+  CHECK(gar_hip_affine_solve_multi(s, 17, rhs.data(), out.data()) == GAR_HIP_OK);
+  // (on the emulator device memory is host memory)
+  CHECK(gar_hip_solution_vectors_device(s, 0, batch, adj.data()) == GAR_HIP_OK);
+  CHECK(gar_hip_download_packed(s, 0, batch, packed.data()) == GAR_HIP_OK);
+  CHECK(gar_hip_upload_packed_user_device(s, 0, batch, packed.data()) == GAR_HIP_OK);
+  CHECK(gar_hip_sync(s) == GAR_HIP_OK);
+}
+void resident_services() {
+  const int batch = 2;
+  Problem p = make_problem(8, 4, 0, 3);
+  const std::vector<int32_t> dims = p.dims5();
+  gar_hip_solver *s = gar_hip_solver_create(0, 3, dims.data(), p.nc0(), batch, 1);
+  CHECK(s != nullptr);
+  if (!s)
+    return;
+  upload(s, p, batch);
+  solve(s);
+  resident_calls(s, batch);
+  CHECK(gar_hip_cycle_append(s, p.knots[0].d) == GAR_HIP_OK); // same dimensions: the ring, every work area stays
+  solve(s);
+  resident_calls(s, batch);
+  const Knot other = make_knot(8, 5, 0, 8);
+  CHECK(gar_hip_cycle_append(s, other.d) == GAR_HIP_OK); // other dimensions: rebuilt, every work area live
+  p.knots.erase(p.knots.begin());
+  p.knots.insert(p.knots.end() - 1, other);
+  upload(s, p, batch);
+  solve(s);
+  resident_calls(s, batch);
+  gar_hip_solver_destroy(s);
+}
+
 struct Scenario {
   const char *name;
   void (*run)();
@@ -327,6 +375,7 @@ const Scenario kExpected[] = {
     {"6 serial fold, ring cycle_append", serial_fold, 14},
     {"7 two devices behind one handle", multi_device, 62},
     {"8 refusals", refusals, 11},
+    {"9 resident services live, ring and rebuilding cycle_append, batch 2", resident_services, 64},
 };
 
 } // namespace
@@ -336,7 +385,7 @@ int main() {
     const long long a0 = gar_hip_debug_alloc_count();
     sc.run();
     const long long n = gar_hip_debug_alloc_count() - a0;
-    std::printf("scenario %-48s allocations %lld (expected %lld)\n", sc.name, n, sc.allocs);
+    std::printf("scenario %-68s allocations %lld (expected %lld)\n", sc.name, n, sc.allocs);
     if (n != sc.allocs) {
       std::printf("  allocation count differs\n");
       ++g_failures;

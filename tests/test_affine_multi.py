@@ -98,6 +98,10 @@ def test_allocation_counts():
     amc.check_allocation(LIB, rounds=20)
 
 
+def test_rebuild_with_every_service_live():
+    amc.check_rebuild_with_services_live(LIB)
+
+
 @pytest.mark.parametrize("pipeline", [False, True], ids=["plain", "pipelined"])
 def test_no_host_synchronisation(pipeline):
     amc.check_no_host_sync(LIB, pipeline=pipeline)
